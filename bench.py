@@ -8,16 +8,24 @@ general-path re-runs, dense CSR compaction), exactly the C-ABI the drop-in
 uses.  Multi-GPU: the corpus is sharded (each rank encodes its own 10M
 sentences, no collective on the data path) → "scaling": "weak".
 
-Prints ONE JSON line on rank 0 with `roofline` (the fast kernel, HIP-event
-timed on the encode stream, plus the trie-probe rate), `cpu_baseline` (the
-CPU oracle port on a bounded sample, 16 threads = the GPU box's CPU share,
-and 1 thread) and the other legs: `bpe_c3` (c3, its own roofline),
-`e2e_raw` (raw text → final ids), `estep` (c4, PARITY mode), `latency`,
-`train` (c5) and `train_bpe` (N=1 only).  The line keeps the numbers (about
-5 KB, ending with a `legs` summary: value, roofline frac and PMC traffic per
-leg); notes, logs and per-batch tables go to the --detail side file.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline
+needs: it draws the corpus, warms up, times the K steps and prints the line
+with `roofline` (the fast kernel, HIP-event timed on the encode stream inside
+the timed steps).  `--dump-outputs DIR` also writes what the last timed step
+computed as DIR/<name>.npy (see dump_outputs).
+
+`--full` adds everything else: the trie-probe rate, the general-path count
+(one more blocking call), `cpu_baseline` (the CPU oracle port on a bounded
+sample, 16 threads = one GPU's share of the host's CPUs, and 1 thread), the full-size
+parity checks against the oracle and the other legs: `bpe_c3` (c3, its own
+roofline), `ja_multibyte`, `e2e_raw` (raw text → final ids), `estep` (c4,
+PARITY mode), `latency`, `train` (c5) and `train_bpe` (N=1 only).  The line
+keeps the numbers (about 5 KB, ending with a `legs` summary: value, roofline
+frac and PMC traffic per leg); notes, logs and per-batch tables go to the
+--detail side file.  The per-leg options below only matter with `--full`.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--sentences S]
+                  [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 outside torchrun starts N worker processes (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1) before anything touches the
@@ -90,10 +98,20 @@ def parse(argv=None):
     ap.add_argument("--pmc-dir", default=os.path.join(ROOT, "profiles", "pmc"),
                     help="stamped PMC summaries of the shipped kernels (tools/pmc_traffic.py, "
                          "tools/gpu_r06_pmc.sh): a summary counts only when its source stamp matches")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
+    ap.add_argument("--detail", default=None,
                     help="side file for the full per-leg record (notes, logs, per-batch tables); the "
-                         "printed line keeps the numbers")
-    return ap.parse_args(argv)
+                         "printed line keeps the numbers (default with --full: bench_detail.json beside "
+                         "this file; a plain run writes it only when asked)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: CPU baselines, trie-probe stats, the "
+                         "general-path count, full-size parity checks and the c3 / ja / raw / c4 / latency / "
+                         "train legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.full and args.detail is None:
+        args.detail = os.path.join(ROOT, "bench_detail.json")
+    return args
 
 
 def launch_workers(args):
@@ -275,8 +293,52 @@ PMC_KERNELS = {"c2": ["unigram_fast_kernel"],
                                "estep_compact_records_kernel", "estep_fold_kernel"]}
 
 
+DUMP_SENTENCES = 1_000_000  # sentences sampled by --dump-outputs (all of them when the batch is smaller)
+DUMP_TOKENS = 8_000_000     # cap on the sampled sentences' tokens (32 MB of float32 ids)
+
+
+def dump_outputs(path, d_ids, d_tok, n, ntok):
+    """--dump-outputs: the arrays the last timed step left in the caller's
+    output buffers (ids int32[ntok], token offsets int64[n+1]), as float .npy
+    files of at most ~44 MB in all:
+
+      totals.npy        float64[3]  sentences, tokens, sum of ALL token ids
+      sample_index.npy  float64[k]  the sampled sentence numbers (ascending;
+                                    numpy default_rng(2024), every sentence
+                                    when n <= DUMP_SENTENCES), cut so that
+                                    their tokens number at most DUMP_TOKENS
+      token_counts.npy  float32[k]  tokens of each sampled sentence
+      ids.npy           float32[sum(token_counts)]  their ids, concatenated
+
+    The sample depends only on n and on the token counts, so two builds that
+    compute the same output write the same files."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    if n > DUMP_SENTENCES:
+        idx = np.sort(np.random.default_rng(2024).choice(n, size=DUMP_SENTENCES, replace=False))
+    else:
+        idx = np.arange(n, dtype=np.int64)
+    d_idx = torch.from_numpy(idx.astype(np.int64)).to(d_tok.device)
+    start = d_tok[:-1][d_idx]
+    cnt = d_tok[1:][d_idx] - start
+    csum = torch.cumsum(cnt, 0)
+    k = int((csum <= DUMP_TOKENS).sum().item())
+    d_idx, start, cnt, csum = d_idx[:k], start[:k], cnt[:k], csum[:k]
+    tot = int(csum[-1].item()) if k else 0
+    # Position j of the concatenation belongs to sampled sentence s(j): its
+    # source index is start[s] + (j - first output position of s).
+    pos = torch.repeat_interleave(start - (csum - cnt), cnt) + torch.arange(tot, device=d_tok.device)
+    ids = d_ids[pos].to(torch.float32).cpu().numpy()
+    id_sum = int(d_ids[:ntok].sum(dtype=torch.int64).item())
+    np.save(os.path.join(path, "totals.npy"), np.array([n, ntok, id_sum], dtype=np.float64))
+    np.save(os.path.join(path, "sample_index.npy"), d_idx.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "token_counts.npy"), cnt.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(path, "ids.npy"), ids)
+
+
 def encode_leg(args, model_path, steps, warmup, world, rank, dev, dist, pmc_leg, probe_stats, corpus=None,
-               workload=None, period=None, coop=False):
+               workload=None, period=None, coop=False, dump=None):
     """One encode benchmark (c2 unigram or c3 BPE on synthetic text, or a
     given normalized `corpus` (buf, off) described by `workload`) on this
     rank's shard."""
@@ -328,17 +390,21 @@ def encode_leg(args, model_path, steps, warmup, world, rank, dev, dist, pmc_leg,
     fast_ms = dm.drain_kernel_times(sp)
     if int(d_st.item()) != 0 or int(d_tok[-1].item()) != ntok:
         raise RuntimeError("encode status %d / token count changed" % int(d_st.item()))
+    if dump and rank == 0:
+        dump_outputs(dump, d_ids, d_tok, n, ntok)
     check = None
     if rank == 0 and not args.no_parity_check:
         ids_t = d_ids[:ntok].cpu().numpy()
         to_t = d_tok.cpu().numpy()
-    # General-path count (and the piece byte lengths for the parity check)
-    # from one blocking call outside the timed region.
-    d_len = torch.empty(max(total_bytes, 1), dtype=torch.int32, device=dev) if rank == 0 else None
-    dm.encode_device(d_bytes.data_ptr(), d_off.data_ptr(), n, d_ids.data_ptr(), d_tok.data_ptr(),
-                     d_len=d_len.data_ptr() if d_len is not None else None, stream=sp)
-    st = dm.stats()
-    general, gen_ms = st.general_path, [st.general_kernel_ms]
+    # --full: general-path count (and the piece byte lengths for the parity
+    # check) from one blocking call outside the timed region.
+    d_len = torch.empty(max(total_bytes, 1), dtype=torch.int32, device=dev) if (rank == 0 and args.full) else None
+    general, gen_ms, st = None, None, None
+    if args.full:
+        dm.encode_device(d_bytes.data_ptr(), d_off.data_ptr(), n, d_ids.data_ptr(), d_tok.data_ptr(),
+                         d_len=d_len.data_ptr() if d_len is not None else None, stream=sp)
+        st = dm.stats()
+        general, gen_ms = int(st.general_path), [st.general_kernel_ms]
     if rank == 0 and not args.no_parity_check:
         torch.cuda.synchronize(dev)
         again = (np.array_equal(d_ids[:ntok].cpu().numpy(), ids_t) and
@@ -384,9 +450,9 @@ def encode_leg(args, model_path, steps, warmup, world, rank, dev, dist, pmc_leg,
     roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
             "kernel": kname, "kernel_ms": k_ms, "algo_bytes_per_launch": algo_bytes,
-            "general_kernel_ms": float(np.mean(gen_ms))}
+            "general_kernel_ms": float(np.mean(gen_ms)) if gen_ms is not None else None}
     roof.update(tinfo)
-    if coop and tok_counts is not None:
+    if coop and tok_counts is not None and st is not None:
         # Long lines take the cooperative kernel (one sentence per wave,
         # nb >= the model's coop threshold); on real text
         # it dominates the step, so it gets its own roofline: its sentences'
@@ -436,7 +502,7 @@ def encode_leg(args, model_path, steps, warmup, world, rank, dev, dist, pmc_leg,
                                " (mean %.2f B), model %s" % (total_bytes / max(n, 1),
                                                               os.path.relpath(model_path, ROOT)),
                    "sentences_per_gpu": n, "tokens_per_gpu": ntok,
-                   "general_path_sentences": int(general),
+                   "general_path_sentences": general,  # (None without --full: it takes a run of its own)
                    "parallelism": "dp%d (sharded corpus, no collective)" % world},
         "roofline": roof,
         "synth_gen_s": gen_s,
@@ -466,9 +532,19 @@ def main():
     dev = torch.device("cuda", local if world > 1 else 0)
     torch.cuda.set_device(dev)
 
+    if not args.full:
+        # A plain run: the headline leg only, nothing that takes a run of its own.
+        args.no_probe_stats = args.no_cpu_baseline = args.no_parity_check = True
     log("c2 encode leg")
     line, model_bytes = encode_leg(args, args.model, args.steps, args.warmup, world, rank, dev, dist,
-                                   "c2", not args.no_probe_stats)
+                                   "c2", not args.no_probe_stats, dump=args.dump_outputs)
+    if not args.full:
+        if rank == 0:
+            write_detail(args, line)
+            print(json.dumps(compact_line(line, args.detail and os.path.relpath(args.detail, ROOT))), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     if rank == 0 and not args.no_cpu_baseline:
         log("c2 cpu baseline")
         th = min(args.cpu_threads, os.cpu_count() or 1)
@@ -538,17 +614,24 @@ def main():
         par["mismatches_total"] = bad
         line["parity"] = par
     if rank == 0:
-        try:
-            os.makedirs(os.path.dirname(args.detail), exist_ok=True)
-            with open(args.detail, "w") as f:
-                json.dump(line, f, indent=1)
-        except OSError as e:
-            log("detail file not written: %s" % e)
+        write_detail(args, line)
         print(json.dumps(compact_line(line, os.path.relpath(args.detail, ROOT))), flush=True)
     if world > 1:
         dist.destroy_process_group()
     if bad:
         raise ParityError("full-size parity check: %d mismatches (see the line's parity object)" % bad)
+
+
+def write_detail(args, line):
+    """The full per-leg record, to the --detail side file (if there is one)."""
+    if not args.detail:
+        return
+    try:
+        os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
+        with open(args.detail, "w") as f:
+            json.dump(line, f, indent=1)
+    except OSError as e:
+        log("detail file not written: %s" % e)
 
 
 ROOF_KEYS = ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms", "algo_bytes_per_launch",

@@ -56,6 +56,53 @@ def test_parity_encode_periodic_reference_equals_direct():
     assert bench.parity_encode(mb, buf, off, ids2, plens, to, 2, period=50)["mismatches"] == 1
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.detail is None and a.steps == 7
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d" and a.detail.endswith("bench_detail.json")
+
+
+def test_dump_outputs_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float .npy files holding the totals of the whole output
+    and, for a seeded sample of sentences cut at the token cap, their token
+    counts and ids; the same output gives the same files."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    n = 1000
+    cnt = rng.integers(0, 9, size=n)
+    tok = np.zeros(n + 1, dtype=np.int64)
+    tok[1:] = np.cumsum(cnt)
+    ntok = int(tok[-1])
+    ids = rng.integers(0, 32000, size=ntok + 50).astype(np.int32)  # (the buffer is larger than the output)
+
+    def run(d):
+        bench.dump_outputs(str(d), torch.from_numpy(ids), torch.from_numpy(tok), n, ntok)
+        return {k: np.load(d / (k + ".npy")) for k in ("totals", "sample_index", "token_counts", "ids")}
+
+    # every sentence (n below the sample size, tokens below the cap)
+    full = run(tmp_path / "a")
+    assert full["totals"].dtype == np.float64 and full["ids"].dtype == np.float32
+    assert full["totals"].tolist() == [n, ntok, float(ids[:ntok].astype(np.int64).sum())]
+    assert np.array_equal(full["sample_index"], np.arange(n))
+    assert np.array_equal(full["token_counts"], cnt) and np.array_equal(full["ids"], ids[:ntok])
+    # a sample, cut at the token cap
+    monkeypatch.setattr(bench, "DUMP_SENTENCES", 100)
+    monkeypatch.setattr(bench, "DUMP_TOKENS", 300)
+    s = run(tmp_path / "b")
+    idx = s["sample_index"].astype(np.int64)
+    assert 0 < len(idx) < 100 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(s["token_counts"], cnt[idx]) and cnt[idx].sum() <= 300
+    assert np.array_equal(s["ids"], np.concatenate([ids[tok[i]:tok[i + 1]] for i in idx]))
+    again = run(tmp_path / "c")
+    assert all(np.array_equal(s[k], again[k]) for k in s)
+
+
 def test_compact_line_fits_the_driver_tail():
     """The printed line keeps every leg's numbers within ~6 KB (the driver's
     output tail keeps ~9 KB) and ends with the `legs` summary; the round-5

@@ -11,7 +11,7 @@ for B in $V; do
   env $VAR=$B timeout -k 10 300 python3 -u -m pytest $R/tests/test_gpu_estep.py -x -q -m gpu --timeout 120 --timeout-method thread > $O/tests_$B.log 2>&1 || { echo "TESTS $B FAILED"; tail -30 $O/tests_$B.log; exit 1; }
   echo "$VAR=$B: $(tail -1 $O/tests_$B.log)"
 done
-ARGS="--steps 1 --warmup 1 --bpe-steps 0 --raw-steps 0 --train-lines 0 --no-cpu-baseline --no-probe-stats --estep-epochs 2 --estep-parity-epochs 2"
+ARGS="--full --steps 1 --warmup 1 --bpe-steps 0 --raw-steps 0 --train-lines 0 --no-cpu-baseline --no-probe-stats --estep-epochs 2 --estep-parity-epochs 2"
 for B in $V; do
   env $VAR=$B timeout -k 10 300 python3 $R/bench.py $ARGS > $O/bench_$B.json 2> $O/bench_$B.err || { echo "BENCH $B FAILED"; tail -5 $O/bench_$B.err; exit 1; }
   python3 -c "

@@ -4,7 +4,7 @@
 # the script stops at the first failure.
 # Usage (via gpurun): bash tools/gpu_r06.sh TAG "TEST_ARGS" "BENCH_ARGS"
 #   TEST_ARGS  pytest selection ("" = skip tests, "all" = every GPU test)
-#   BENCH_ARGS bench.py arguments ("" = skip the bench, "default" = none)
+#   BENCH_ARGS bench.py arguments ("" = skip the bench, "default" = --full alone)
 set -o pipefail
 TAG=${1:-r06}
 TESTS=${2:-}
@@ -20,7 +20,7 @@ if [ -n "$TESTS" ]; then
   tail -1 $O/gpu_tests.log
 fi
 if [ -n "$BENCH" ]; then
-  [ "$BENCH" = "default" ] && BENCH=""
+  [ "$BENCH" = "default" ] && BENCH="--full"
   timeout -k 10 1000 python3 -u $R/bench.py $BENCH > $O/bench.json 2> $O/bench.err || { echo "BENCH FAILED"; tail -20 $O/bench.err; exit 1; }
   python3 $R/tools/bench_summary.py $O/bench.json
 fi

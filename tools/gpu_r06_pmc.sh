@@ -16,7 +16,7 @@ mkdir -p $O $O/pmc
 cd /tmp && export TMPDIR=/tmp
 # The PMC databases stay on the box whatever happens (gpurun copies back at most 64 MiB).
 trap 'find $O -name "*.db" -delete' EXIT
-OFF="--raw-steps 0 --train-lines 0 --bpe-train-lines 0 --latency-calls 0 --no-cpu-baseline --no-probe-stats --no-parity-check"
+OFF="--full --raw-steps 0 --train-lines 0 --bpe-train-lines 0 --latency-calls 0 --no-cpu-baseline --no-probe-stats --no-parity-check"
 pass() {  # name counter args...
   local name=$1 ctr=$2; shift 2
   timeout -s KILL 300 rocprofv3 --pmc $ctr --kernel-trace -d $O/$name -o run -- python3 $R/bench.py "$@" --detail $O/$name.detail.json > $O/$name.log 2>&1 || { echo "PMC $name FAILED"; tail -5 $O/$name.log; exit 1; }

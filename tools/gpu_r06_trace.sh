@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-OFF="--raw-steps 0 --train-lines 0 --bpe-train-lines 0 --latency-calls 0 --no-cpu-baseline --no-probe-stats --no-parity-check"
+OFF="--full --raw-steps 0 --train-lines 0 --bpe-train-lines 0 --latency-calls 0 --no-cpu-baseline --no-probe-stats --no-parity-check"
 for leg in $LEGS; do
   case $leg in
     enc) A="--steps 3 --warmup 1 --sentences 10000000 --bpe-steps 3 --ja-lines 0 --estep-sentences 0 $OFF" ;;
