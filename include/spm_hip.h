@@ -525,6 +525,17 @@ int spm_hip_model_trie_stats(const spm_hip_model *model, const uint8_t *norm_byt
                              const uint64_t *offsets, uint64_t n, int num_threads,
                              spm_hip_trie_stats *out);
 
+/* Diagnostic (works on host-only handles): looks bytes[0:len) up in the
+ * piece -> (id, node score) table the byte kernel's backtrace reads, on the
+ * host copy and with the kernel's hash and probe sequence.  SPM_OK: found,
+ * *id and *score (nullable) are the usable trie node's id and score (a
+ * USER_DEFINED piece: chars * max_score + 1).  SPM_NOT_FOUND: no usable
+ * node has these bytes (UNUSED pieces, inner nodes, an embedded NUL, the
+ * empty key, more than 15 bytes).  SPM_FAILED_PRECONDITION: the model has no
+ * such table (not a byte-kernel model). */
+int spm_hip_model_piece_lookup(const spm_hip_model *model, const uint8_t *bytes, uint64_t len, int32_t *id,
+                               float *score);
+
 /* Raw lines -> the final ids of SentencePieceProcessor::Encode(line, &ids)
  * (sentencepiece_processor.cc:319-330: Normalizer::Normalize, normalizer.cc:
  * 88-211; ModelInterface::Encode, unigram_model.cc:705-720; the unknown-run

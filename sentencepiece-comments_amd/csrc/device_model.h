@@ -146,6 +146,11 @@ struct spm_hip_model {
   // byte kernel: per unit (d_units with empty units = label 0xFF, usable-node
   // score or NaN) interleaved
   spm_amd::DevBuf d_uvs;
+  // byte kernel: piece bytes -> (id, node score) of the usable trie nodes
+  // (piece_table.h: header + entries; empty when the probe bound could not
+  // be proven).  The host copy serves spm_hip_model_piece_lookup.
+  std::vector<uint32_t> piece_table;
+  spm_amd::DevBuf d_piece_tab;
   spm_amd::BpeDevice bpe;
   // Lazily uploaded tables (under init_mu): device normalizer charsmap blob +
   // user-defined trie; id-epilogue piece type bits.

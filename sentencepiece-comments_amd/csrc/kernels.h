@@ -49,6 +49,8 @@ struct UnigramLaunch {
   const int32_t *values;
   const float *scores;
   uint32_t num_units;
+  const uint32_t *piece_tab; // byte kernel: piece -> (id, score) table (piece_table.h; nullptr: trie re-walk)
+  uint32_t piece_mask, piece_seed;  // the table's header words
   UnigramParams p;
   int32_t *ids;              // dense output (written by the fix-up / tile compaction)
   uint32_t *len;             // nullable

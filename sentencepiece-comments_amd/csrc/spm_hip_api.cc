@@ -24,6 +24,7 @@
 #include "kernels.h"
 #include "normalize_device.h"
 #include "normalizer.h"
+#include "piece_table.h"
 #include "shard_plan.h"
 #include "trace.h"
 
@@ -81,6 +82,131 @@ int InitializePieces(spm_hip_model *m) {
   if (m->unk_id == -1) return Fail(SPM_INTERNAL, "unk is not defined.");
   std::sort(m->user_defined.begin(), m->user_defined.end());
   return SPM_OK;
+}
+
+// Byte-pass score table: the node score (USER_DEFINED: length * max_score
+// + 1.0, unigram_model.cc:589-591, length = the piece's char count), NaN
+// for units that are no usable node (inner, empty, UNUSED).
+std::vector<float> UsableNodeScores(const spm_hip_model *m, const std::vector<float> &scores) {
+  std::vector<float> vbp(m->trie.units.size(), std::numeric_limits<float>::quiet_NaN());
+  for (size_t u = 0; u < m->trie.units.size(); ++u) {
+    if (!spm_amd::DoubleArray::Leaf(m->trie.units[u])) continue;
+    const int32_t v = m->trie.values[u];
+    const int32_t kind = v >> spm_amd::kKindShift;
+    const int32_t id = v & spm_amd::kIdMask;
+    if (kind == 0) {
+      vbp[u] = scores[id];
+    } else if (kind == spm_amd::kKindUserDefined) {
+      const std::string &pc = m->proto.pieces[id].piece;
+      const int chars = CountChars(pc.substr(0, pc.find('\0')));
+      const float prod = static_cast<float>(chars) * m->max_score;
+      vbp[u] = static_cast<float>(static_cast<double>(prod) + 1.0);
+    }
+  }
+  return vbp;
+}
+
+// The byte kernel's piece -> (id, node score) table (piece_table.h), built
+// from the trie so that a lookup answers exactly what the backtrace's exact
+// -match walk answers: every piece's key (up to its first NUL) is walked, and
+// the node reached is stored, once, if it is usable (non-NaN in vbp).  Each
+// key is placed at one of its two hashed positions (cuckoo insertion; at a
+// load of <= 1/2 a seed works with probability > 0.8, so seeds are retried
+// and the capacity is doubled once), and the result is checked: every key
+// must be found within kPieceProbes entry loads.  Empty on failure (the
+// kernel then keeps its walk).
+std::vector<uint32_t> BuildPieceTable(const spm_hip_model *m, const std::vector<float> &vbp) {
+  using spm_amd::PieceEntry;
+  const auto &units = m->trie.units;
+  std::vector<PieceEntry> keys;
+  std::vector<std::pair<uint32_t, std::string>> nodes;  // (node, key), by node: the order is the trie's
+  for (const auto &kv : m->pieces) {
+    const std::string key = kv.first.substr(0, kv.first.find('\0'));
+    if (key.empty() || key.size() > spm_amd::kPieceKeyBytes) continue;
+    uint32_t nbase = m->up.root_base, node = 0;
+    bool found = true;
+    for (const char ch : key) {
+      const uint32_t c = static_cast<uint8_t>(ch);
+      node = nbase ^ c;
+      if (node >= units.size() || spm_amd::DoubleArray::Label(units[node]) != c) {
+        found = false;
+        break;
+      }
+      nbase = spm_amd::DoubleArray::Base(units[node]);
+    }
+    if (found && !std::isnan(vbp[node])) nodes.emplace_back(node, key);
+  }
+  std::sort(nodes.begin(), nodes.end());
+  nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
+  for (const auto &nk : nodes) {
+    PieceEntry e{};
+    spm_amd::PieceKey(reinterpret_cast<const uint8_t *>(nk.second.data()), static_cast<uint32_t>(nk.second.size()),
+                      e.k);
+    e.id = m->trie.values[nk.first] & spm_amd::kIdMask;
+    e.score = vbp[nk.first];
+    keys.push_back(e);
+  }
+  if (keys.empty()) return {};
+  // The kernel loads a key's second position only when the first misses.
+  // Keys go in by ascending score and a new key always takes its first
+  // position (its holder moves on), so the frequent pieces end up there.
+  std::stable_sort(keys.begin(), keys.end(),
+                   [](const PieceEntry &x, const PieceEntry &y) { return x.score < y.score; });
+  uint32_t cap0 = 16;
+  while (cap0 < 2 * keys.size()) cap0 <<= 1;
+  constexpr uint32_t kSeeds = 64, kMaxKicks = 512;
+  for (uint32_t cap = cap0; cap <= 2 * cap0 && cap <= (1u << 18); cap <<= 1) {
+    const uint32_t mask = cap - 1;
+    for (uint32_t seed = 1; seed <= kSeeds; ++seed) {
+      std::vector<int32_t> slot(cap, -1);
+      auto pos_of = [&](int32_t i, uint32_t *p0, uint32_t *p1) {
+        spm_amd::PieceHash(keys[i].k[0], keys[i].k[1], keys[i].k[2], keys[i].k[3], seed, mask, p0, p1);
+      };
+      bool ok = true;
+      for (size_t i = 0; i < keys.size() && ok; ++i) {
+        int32_t cur = static_cast<int32_t>(i);
+        uint32_t p0, p1;
+        pos_of(cur, &p0, &p1);
+        uint32_t pos = p0;  // a new key takes its first position, whoever holds it
+        ok = false;
+        for (uint32_t kick = 0; kick < kMaxKicks; ++kick) {
+          std::swap(cur, slot[pos]);
+          if (cur < 0) {
+            ok = true;
+            break;
+          }
+          pos_of(cur, &p0, &p1);  // the evicted key goes to its other position
+          pos = pos == p0 ? p1 : p0;
+        }
+      }
+      if (!ok) continue;
+      for (size_t i = 0; i < keys.size(); ++i) {  // a free first position is always better
+        uint32_t p0, p1;
+        pos_of(static_cast<int32_t>(i), &p0, &p1);
+        if (slot[p0] < 0 && slot[p1] == static_cast<int32_t>(i)) std::swap(slot[p0], slot[p1]);
+      }
+      std::vector<uint32_t> img(8 * (static_cast<size_t>(cap) + 1), 0u);
+      img[0] = mask;
+      img[1] = seed;
+      for (uint32_t p = 0; p < cap; ++p) {
+        uint32_t *w = &img[8 * (static_cast<size_t>(p) + 1)];
+        if (slot[p] < 0) {
+          w[3] = spm_amd::kPieceEmpty;
+          continue;
+        }
+        const PieceEntry &e = keys[slot[p]];
+        std::memcpy(w, &e, sizeof(e));
+      }
+      // The probe bound, proven on the finished image with the lookup itself.
+      for (const PieceEntry &e : keys) {
+        int32_t id;
+        float sc;
+        if (!spm_amd::PieceTableFind(img.data(), e.k, &id, &sc) || id != e.id || std::memcmp(&sc, &e.score, 4) != 0) ok = false;
+      }
+      if (ok) return img;
+    }
+  }
+  return {};
 }
 
 // unigram::Model::Model (unigram_model.cc:677-695) + BuildTrie (:624-673).
@@ -163,11 +289,15 @@ int LoadUnigram(spm_hip_model *m) {
   // marks units without a usable node: models with a NaN score keep the
   // lane kernels' path.
   m->coop_min_nb = (nan_score || max_bytes > 56) ? 0u : DefaultCoopMinNb();
+  const bool pair_table = byte_ok || wide_ok || (m->kernel == spm_amd::UnigramKernel::kChar && !nan_score);
+  std::vector<float> vbp;
+  if (pair_table) vbp = UsableNodeScores(m, scores);
+  if (byte_ok) m->piece_table = BuildPieceTable(m, vbp);
   if (m->host_only) return SPM_OK;
   SPM_HIP_TRY(Upload(&m->d_units, m->trie.units));
   SPM_HIP_TRY(Upload(&m->d_values, m->trie.values));
   SPM_HIP_TRY(Upload(&m->d_scores, scores));
-  if (byte_ok || wide_ok || (m->kernel == spm_amd::UnigramKernel::kChar && !nan_score)) {
+  if (pair_table) {
     // Empty units get label 0xFF so a walk needs no NUL test: real labels
     // are never 0 (keys stop at NUL) and a 0xFF input byte flags the sentence.
     // The root (unit 0, label 0) gets 0xFF too: a childless node has base 0,
@@ -176,24 +306,6 @@ int LoadUnigram(spm_hip_model *m) {
     for (size_t u = 1; u < ff.size(); ++u)
       if (ff[u] == 0) ff[u] = 0xFFu;
     if (!ff.empty()) ff[0] |= 0xFFu;
-    // Byte-pass score table: the node score (USER_DEFINED: length * max_score
-    // + 1.0, unigram_model.cc:589-591, length = the piece's char count), NaN
-    // for units that are no usable node (inner, empty, UNUSED).
-    std::vector<float> vbp(m->trie.units.size(), std::numeric_limits<float>::quiet_NaN());
-    for (size_t u = 0; u < m->trie.units.size(); ++u) {
-      if (!spm_amd::DoubleArray::Leaf(m->trie.units[u])) continue;
-      const int32_t v = m->trie.values[u];
-      const int32_t kind = v >> spm_amd::kKindShift;
-      const int32_t id = v & spm_amd::kIdMask;
-      if (kind == 0) {
-        vbp[u] = scores[id];
-      } else if (kind == spm_amd::kKindUserDefined) {
-        const std::string &pc = m->proto.pieces[id].piece;
-        const int chars = CountChars(pc.substr(0, pc.find('\0')));
-        const float prod = static_cast<float>(chars) * m->max_score;
-        vbp[u] = static_cast<float>(static_cast<double>(prod) + 1.0);
-      }
-    }
     // One (unit, score) pair per unit: the walk reads both with one 8-byte
     // gather per step.
     std::vector<uint32_t> uvs(2 * ff.size());
@@ -202,6 +314,10 @@ int LoadUnigram(spm_hip_model *m) {
       std::memcpy(&uvs[2 * u + 1], &vbp[u], 4);
     }
     SPM_HIP_TRY(Upload(&m->d_uvs, uvs));
+    // The backtrace's piece table (A/B knob: SPM_HIP_NO_PIECE_TABLE leaves the
+    // pointer null and the kernel re-walks the trie).
+    if (!m->piece_table.empty() && std::getenv("SPM_HIP_NO_PIECE_TABLE") == nullptr)
+      SPM_HIP_TRY(Upload(&m->d_piece_tab, m->piece_table));
   }
   return SPM_OK;
 }
@@ -245,6 +361,11 @@ spm_amd::UnigramLaunch UnigramTables(spm_hip_model *m, const spm_amd::EncodeCall
   l.values = m->d_values.as<int32_t>();
   l.scores = m->d_scores.as<float>();
   l.num_units = static_cast<uint32_t>(m->trie.units.size());
+  l.piece_tab = m->d_piece_tab.as<uint32_t>();
+  if (l.piece_tab) {
+    l.piece_mask = m->piece_table[0];
+    l.piece_seed = m->piece_table[1];
+  }
   l.p = m->up;
   l.ids = c.ids;
   l.len = c.len;
@@ -951,7 +1072,7 @@ int spm_hip_model_load_host_only(const void *model_proto, size_t len, spm_hip_mo
 
 void spm_hip_model_free(spm_hip_model *m) {
   if (!m) return;
-  for (spm_amd::DevBuf *b : {&m->d_units, &m->d_uvs, &m->d_values, &m->d_scores,
+  for (spm_amd::DevBuf *b : {&m->d_units, &m->d_uvs, &m->d_piece_tab, &m->d_values, &m->d_scores,
                              &m->bpe.pair_keys, &m->bpe.pair_vals, &m->bpe.pair_ent, &m->bpe.rank_piece, &m->bpe.entry_piece,
                              &m->bpe.entry_out, &m->bpe.piece_kind, &m->bpe.piece_out,
                              &m->d_charsmap, &m->d_ud_units, &m->d_types})
@@ -973,6 +1094,21 @@ int spm_hip_model_get_info(const spm_hip_model *m, spm_hip_model_info *info) {
   info->max_score = m->max_score;
   info->ring_width = m->model_type == spm_amd::kUnigram ? m->ring_width : 0;
   info->fast_variant = m->model_type == spm_amd::kUnigram ? static_cast<int32_t>(m->kernel) : 0;
+  return SPM_OK;
+}
+
+int spm_hip_model_piece_lookup(const spm_hip_model *m, const uint8_t *bytes, uint64_t len, int32_t *id,
+                               float *score) {
+  if (!m || (len && !bytes)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (m->piece_table.empty()) return Fail(SPM_FAILED_PRECONDITION, "the model has no piece table");
+  if (len == 0 || len > spm_amd::kPieceKeyBytes) return SPM_NOT_FOUND;
+  uint32_t k[4];
+  spm_amd::PieceKey(bytes, static_cast<uint32_t>(len), k);
+  int32_t i = 0;
+  float s = 0.f;
+  if (!spm_amd::PieceTableFind(m->piece_table.data(), k, &i, &s)) return SPM_NOT_FOUND;
+  if (id) *id = i;
+  if (score) *score = s;
   return SPM_OK;
 }
 

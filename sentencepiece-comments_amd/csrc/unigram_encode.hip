@@ -52,6 +52,7 @@
 #include "device_common.h"
 #include "kernels.h"
 #include "lookback.h"  // status words
+#include "piece_table.h"
 
 namespace spm_amd {
 namespace {
@@ -86,6 +87,8 @@ struct FastArgs {
   uint32_t *host_pub;              // single-tile host call: status words + sequence to host memory
   uint32_t pub_seq;
   uint32_t coop_min_nb;            // wide / char kernels: longer sentences go to the cooperative kernel
+  const uint32_t *__restrict__ piece_tab;  // byte kernel: piece -> (id, score) table (piece_table.h), nullable
+  uint32_t piece_mask, piece_seed;         // its header words
 };
 
 constexpr int kBlock = 256;
@@ -925,6 +928,50 @@ void unigram_fast_kernel(FastArgs a) {
       }
       uint32_t r0 = __builtin_amdgcn_alignbyte(w[1], w[0], sh), r1 = __builtin_amdgcn_alignbyte(w[2], w[1], sh);
       uint32_t r2 = __builtin_amdgcn_alignbyte(w[3], w[2], sh), r3 = __builtin_amdgcn_alignbyte(w[4], w[3], sh);
+      if constexpr (!kE) {
+        if (a.piece_tab) {
+          // The forward pass already stood on this token's node: instead of
+          // walking its bytes from the root again (one dependent gather per
+          // byte, in wave lockstep the longest token of 64 lanes), look the
+          // bytes up in the piece table.  The key is the token's bytes
+          // zero-padded, the length in the last byte; the table holds exactly
+          // the usable trie nodes, so a miss is what the walk calls UNK (an
+          // inner or UNUSED node, no node, a NUL inside the token).
+          const uint32_t len = e - b;
+          const int n = static_cast<int>(len);
+          auto keep = [](uint32_t r, int nb) { return nb >= 4 ? r : nb <= 0 ? 0u : r & ~(~0u << (8 * nb)); };
+          const uint32_t k0 = keep(r0, n), k1 = keep(r1, n - 4), k2 = keep(r2, n - 8);
+          const uint32_t k3 = (keep(r3, n - 12) & 0x00FFFFFFu) | (len << 24);
+          // (mask and seed come as kernel arguments: read from the table's
+          // header they are vector loads behind the kernel's stores, and the
+          // resource built from them is no longer wave-uniform.)
+          const uint32_t tmask = a.piece_mask, tseed = a.piece_seed;
+          const auto tab_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+              const_cast<uint32_t *>(a.piece_tab), 0, static_cast<int>((tmask + 2u) * 32u), 0x00020000);
+          uint32_t p0, p1;
+          PieceHash(k0, k1, k2, k3, tseed, tmask, &p0, &p1);
+          const uint32_t o0 = (p0 + 1u) * 32u, o1 = (p1 + 1u) * 32u;
+          const auto ka = __builtin_amdgcn_raw_buffer_load_b128(tab_rsrc, o0, 0, 0);
+          const auto va = __builtin_amdgcn_raw_buffer_load_b64(tab_rsrc, o0 + 16u, 0, 0);
+          bool hit = ka[0] == k0 && ka[1] == k1 && ka[2] == k2 && ka[3] == k3;
+          uint32_t idv = va[0], scv = va[1];
+          // The second position only for the lanes that missed the first (the
+          // builder puts the frequent pieces first): loaded for every lane it
+          // pulled a cold, mostly empty line per token through the L2
+          // (TCC_MISS 9.2e6 -> 1.67e7 per launch).
+          if (!hit) {
+            const auto kb = __builtin_amdgcn_raw_buffer_load_b128(tab_rsrc, o1, 0, 0);
+            const auto vb = __builtin_amdgcn_raw_buffer_load_b64(tab_rsrc, o1 + 16u, 0, 0);
+            hit = kb[0] == k0 && kb[1] == k1 && kb[2] == k2 && kb[3] == k3;
+            idv = vb[0];
+            scv = vb[1];
+          }
+          hit = hit && len - 1u < kPieceKeyBytes;
+          *id_out = hit ? static_cast<int32_t>(idv) : a.p.unk_id;
+          *sc_out = hit ? __uint_as_float(scv) : a.p.unk_score;
+          return;
+        }
+      }
       const auto uvs_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(a.units), 0,
                                                               static_cast<int>(a.num_units * 8u), 0x00020000);
       uint32_t nbase = a.p.root_base, node = 0, u = 0, scb = 0;
@@ -1305,7 +1352,7 @@ hipError_t LaunchUnigramFast(UnigramKernel kind, int W, const UnigramLaunch &l, 
   FastArgs a{l.bytes, l.off, l.n, l.capacity, l.units, l.values, l.scores, l.num_units, l.p, l.ids, l.len,
              l.tok_off, l.bp, l.flagged, l.status, l.tile_count, l.corrupt_bp, l.chain, l.slot_ids, l.slot_len,
              EStepForwardOut{}, l.bpn, l.stage_src, l.stage_dst, l.stage_zero, l.stage_words, l.host_pub, l.pub_seq,
-             l.coop_min_nb};
+             l.coop_min_nb, l.piece_tab, l.piece_mask, l.piece_seed};
   const uint64_t blocks64 = FastTiles(l.n);
   if (blocks64 == 0) return hipSuccess;
   if (blocks64 > 0x7FFFFFFFull) return hipErrorInvalidValue;

@@ -40,7 +40,7 @@ EXPORTED = [
     "spm_hip_model_release_stream", "spm_hip_abi_version", "spm_hip_seeds_stage_times",
     "spm_hip_estep_record_stats", "spm_hip_estep_bucket_owner", "spm_hip_pieces_set_timing",
     "spm_hip_estep_kernel_times", "spm_hip_device_bytes", "spm_hip_device_peak_reset",
-    "spm_hip_encode_raw_small_host",
+    "spm_hip_encode_raw_small_host", "spm_hip_model_piece_lookup",
 ]
 
 ABI_VERSION = 3  # SPM_HIP_ABI_VERSION of include/spm_hip.h (struct layouts below)
@@ -190,6 +190,8 @@ def lib():
         L.spm_hip_seeds_free.restype = None
         L.spm_hip_seed_last_error.restype = ctypes.c_char_p
         L.spm_hip_model_trie_stats.argtypes = [P, P, P, U64, I, ctypes.POINTER(TrieStats)]
+        L.spm_hip_model_piece_lookup.argtypes = [P, ctypes.c_char_p, U64, ctypes.POINTER(ctypes.c_int32),
+                                                 ctypes.POINTER(ctypes.c_float)]
         L.spm_hip_device_bytes.argtypes = [ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_encode_raw_small_host.argtypes = [P, P, P, U64, P, U64, P]
         L.spm_hip_device_peak_reset.restype = None
@@ -246,6 +248,16 @@ class DeviceModel:
         _check(self._L.spm_hip_model_trie_stats(self.h, _p(buf), _p(off), len(off) - 1, threads,
                                                  ctypes.byref(ts)))
         return ts
+
+    def piece_lookup(self, key):
+        """Diagnostic: (id, score) of `key` in the byte kernel's piece table, None on a miss."""
+        i, s = ctypes.c_int32(0), ctypes.c_float(0.0)
+        b = bytes(key)
+        rc = self._L.spm_hip_model_piece_lookup(self.h, b, len(b), ctypes.byref(i), ctypes.byref(s))
+        if rc == 5:  # SPM_NOT_FOUND
+            return None
+        _check(rc)
+        return i.value, s.value
 
     def stats(self):
         st = EncodeStats()
