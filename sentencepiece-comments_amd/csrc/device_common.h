@@ -46,6 +46,22 @@ __device__ __forceinline__ bool NearTieHi(float lo, float hi, float mag) {
   return __fsub_rn(hi, lo) <= (fabsf(hi) + mag) * 9.5367431640625e-7f;  // 2^-20
 }
 
+// NearTieHi with the bound taken once per begin position instead of once per
+// node: every setter hi of that position is fl(t0 + s) with |s| <= mag, and
+//   TieBound(t0, mag) = fl(fl(|t0| + mag) + mag)·2^-20
+// is at least NearTieHi's right-hand side fl(|hi| + mag)·2^-20 for each of
+// them.  Proof: |t0 + s| <= |t0| + mag in the reals; rounding to nearest is
+// monotone and odd, so |hi| = fl(|t0 + s|) <= fl(|t0| + mag), and again
+// fl(|hi| + mag) <= fl(fl(|t0| + mag) + mag); the factor 2^-20 is exact on
+// both sides (mag >= 1: no underflow).  Hence NearTie => NearTieHi =>
+// NearTieAt: a superset, two operations per node instead of four.  False for
+// lo = -inf (hi - lo = +inf) whenever t0 is finite, which it is at a char
+// start, and for a NaN hi.
+__device__ __forceinline__ float TieBound(float t0, float mag) {
+  return __fadd_rn(__fadd_rn(fabsf(t0), mag), mag) * 9.5367431640625e-7f;  // 2^-20
+}
+__device__ __forceinline__ bool NearTieAt(float lo, float hi, float bound) { return __fsub_rn(hi, lo) <= bound; }
+
 // LogSumExp of unigram_model.cc:51-63: float storage, double exp/log.
 __device__ __forceinline__ float LogSumExpDev(float x, float y, bool init_mode) {
   if (init_mode) return y;

@@ -91,6 +91,29 @@ struct FastArgs {
   uint32_t piece_mask, piece_seed;         // its header words
 };
 
+// Byte kB of w = kV (an inline constant, 0..64) in the lanes of wave mask m:
+// one sub-dword select.  (Written as and / or / select the compiler spends
+// two literal operations and a select on every byte but the lowest.)  The
+// s_nop keeps the next instruction, which the compiler's hazard check cannot
+// see into an asm for, one wait state from the sub-dword write (gfx940+: a
+// vector instruction must not read such a result in the very next issue).
+template <int kB, int kV>
+__device__ __forceinline__ void SetByteIf(uint32_t &w, uint64_t m) {
+  static_assert(kB >= 0 && kB < 4 && kV >= 0 && kV <= 64, "a byte of a dword, an inline constant");
+  if constexpr (kB == 0)
+    __asm__("s_mov_b64 vcc, %1\n\tv_cndmask_b32_sdwa %0, %0, %2, vcc dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE "
+            "src0_sel:BYTE_0 src1_sel:DWORD\n\ts_nop 0" : "+v"(w) : "s"(m), "n"(kV) : "vcc");
+  else if constexpr (kB == 1)
+    __asm__("s_mov_b64 vcc, %1\n\tv_cndmask_b32_sdwa %0, %0, %2, vcc dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE "
+            "src0_sel:BYTE_1 src1_sel:DWORD\n\ts_nop 0" : "+v"(w) : "s"(m), "n"(kV) : "vcc");
+  else if constexpr (kB == 2)
+    __asm__("s_mov_b64 vcc, %1\n\tv_cndmask_b32_sdwa %0, %0, %2, vcc dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE "
+            "src0_sel:BYTE_2 src1_sel:DWORD\n\ts_nop 0" : "+v"(w) : "s"(m), "n"(kV) : "vcc");
+  else
+    __asm__("s_mov_b64 vcc, %1\n\tv_cndmask_b32_sdwa %0, %0, %2, vcc dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE "
+            "src0_sel:BYTE_3 src1_sel:DWORD\n\ts_nop 0" : "+v"(w) : "s"(m), "n"(kV) : "vcc");
+}
+
 constexpr int kBlock = 256;
 constexpr int kLdsBpPos = 64;  // back-pointer bytes kept in LDS per lane
 constexpr int kEStepWaves = 4;  // E-step forward mode (alpha ring + fp64 LogSumExp)
@@ -131,7 +154,7 @@ void unigram_fast_kernel(FastArgs a) {
   constexpr uint32_t kStageIds = kStage ? 1264u : 2u;
   __shared__ uint2 lds_union[kStageIds / 2];
   __shared__ uint32_t lds_sort_own[kStage ? 1 : 2 * kBlock];
-  __shared__ uint2 lds_root_own[(kRootLds && !kStage) ? kBlock : 1];
+  __shared__ uint2 lds_root_own[(kRootLds && !kStage) ? kBlock + (kE ? 1 : 0) : 1];  // kE: + the byte pass's entry 256
   uint32_t *const lds_stage = reinterpret_cast<uint32_t *>(lds_union);
   uint32_t *const lds_sort = kStage ? lds_stage : lds_sort_own;
   uint2 *const lds_root = kStage ? lds_union + kBlock : lds_root_own;
@@ -165,7 +188,22 @@ void unigram_fast_kernel(FastArgs a) {
   if (tid == 0) lds_tile = atomicAdd(&a.status[kStTicket], 1u);
   if constexpr (kRootLds) {
     const uint32_t nd = a.p.root_base ^ static_cast<uint32_t>(tid);
-    lds_root[tid] = nd < a.num_units ? reinterpret_cast<const uint2 *>(a.units)[nd] : make_uint2(0u, 0u);
+    uint2 r = nd < a.num_units ? reinterpret_cast<const uint2 *>(a.units)[nd] : make_uint2(0u, 0u);
+    if constexpr (kByte) {
+      // The byte pass takes a position's depth-1 node score from this table
+      // as it stands: NaN unless byte `tid` has a root child, and for a
+      // one-byte char (NUL included) the UNK node's score when it has no
+      // usable single-char node (unigram_model.cc:597-601), so the forward
+      // pass needs no UNK select for ASCII.  Only the score changes: the
+      // backtrace looks the token up by its bytes, misses and emits unk_id.
+      float sc = (r.x & 0xFFu) == static_cast<uint32_t>(tid) ? __uint_as_float(r.y) : __builtin_nanf("");
+      if (tid < 0x80 && __builtin_isnan(sc)) sc = a.p.unk_score;
+      r.y = __float_as_uint(sc);
+      // Entry 256: what a position that is no char start reads (label 0xFF
+      // matches no byte of an unflagged sentence, no node).
+      if (tid == 0) lds_root[kBlock] = make_uint2(0xFFu, __float_as_uint(__builtin_nanf("")));
+    }
+    lds_root[tid] = r;
   }
   __syncthreads();
   const uint64_t tile = lds_tile;
@@ -390,17 +428,30 @@ void unigram_fast_kernel(FastArgs a) {
       constexpr int t = decltype(tc)::value;
       return (rw[t >> 2] >> (8 * (t & 3))) & 0xFFu;
     };
-    // Node [p, p + d) of position j with raw score sc (NaN: no usable node)
-    // into slot j + d.  Nodes reach a slot in ascending begin order.
-    auto insert_one = [&](auto jc, auto dc, uint32_t p, float T0, float A0, uint32_t clen0, bool st, float sc,
-                          int dmax) {
+    // The hot path keeps its per-lane predicates as wave masks in scalar
+    // registers: a ballot of a compare is the compare itself, masks combine
+    // on the scalar unit, and a select takes the mask as it is.  (A ballot of
+    // a bool built from two conditions costs a 0/1 select and a second
+    // compare on the vector unit, the bound of this kernel.)
+    using Mask = uint64_t;
+    auto lanes_of = [](Mask m) -> bool { return __builtin_amdgcn_inverse_ballot_w64(m); };
+    bool amb_wave = false;  // wave-uniform: some lane has an open near-tie entry (ambm != 0)
+    // Node [p, p + d) of position j with score sc (NaN: no usable node) into
+    // slot j + d.  Nodes reach a slot in ascending begin order.  sc is NaN at
+    // a position that is no char start, and holds a one-byte char's UNK node
+    // already (the root table); ucl = the char's length where it has two or
+    // more bytes (or is a stray tail byte), 0 elsewhere, unk_any = some lane
+    // of the wave has ucl != 0.
+    auto insert_one = [&](auto jc, auto dc, uint32_t p, float T0, float tie_bound, float A0, uint32_t ucl,
+                          bool unk_any, float sc, int dmax) {
       constexpr int j = decltype(jc)::value;
       constexpr int d = decltype(dc)::value;
-      if (d > 4 && d > dmax) return;
+      if (d > 1 && d > dmax && !(d <= 4 && unk_any)) return;
       float s_node = sc;
       // UNK node (unigram_model.cc:597-601): no usable single-char node.
-      if constexpr (d <= 4) s_node = (d == static_cast<int>(clen0) && __builtin_isnan(s_node)) ? a.p.unk_score : s_node;
-      if (!st) s_node = __builtin_nanf("");
+      if constexpr (d <= 4) {
+        if (unk_any) s_node = (d == static_cast<int>(ucl) && __builtin_isnan(s_node)) ? a.p.unk_score : s_node;
+      }
       const float bt = __fadd_rn(T0, s_node);
       constexpr int k = j + d;
       if constexpr (kE) {
@@ -409,24 +460,32 @@ void unigram_fast_kernel(FastArgs a) {
           ++e_nodes;
         }
       }
-      const bool gt = bt > T[k];  // false for NaN
-      const bool rare = gt && (NearTieHi(T[k], bt, tie_mag) || ((ambm >> k) & 1));
-      if (__builtin_amdgcn_ballot_w64(rare) != 0) {
-        if (rare)
-          amb_update(std::integral_constant<int, k>{}, bt, NearTieHi(T[k], bt, tie_mag), p + d, T[k],
+      // A slot's first setter of depth W - 1 finds the -inf the ring shift
+      // put there, a constant to the compiler, which folds bt > -inf to an
+      // ordered "!=" and then selects the UNORDERED compare for its ballot
+      // (v_cmp_neq: true for a NaN bt, which then stays in the slot for good).
+      // The slot's value is made opaque there, so the compare stays ">".
+      float tk = T[k];
+      if constexpr (d == W - 1) __asm__ volatile("" : "+v"(tk));
+      const Mask gtm = __builtin_amdgcn_ballot_w64(bt > tk);  // false for NaN
+      const Mask nearm = gtm & __builtin_amdgcn_ballot_w64(NearTieAt(tk, bt, tie_bound));
+      if (nearm != 0 || amb_wave) {
+        const bool nr = lanes_of(nearm);
+        if (nr || (lanes_of(gtm) && ((ambm >> k) & 1)))
+          amb_update(std::integral_constant<int, k>{}, bt, nr, p + d, T[k],
                      p + d - b_dist(std::integral_constant<int, k>{}));
+        amb_wave = __builtin_amdgcn_ballot_w64(ambm != 0) != 0;
       }
-      T[k] = gt ? bt : T[k];
-      constexpr uint32_t sh8 = 8 * (k & 3);
-      const uint32_t w = (Bw[k >> 2] & ~(0xFFu << sh8)) | (static_cast<uint32_t>(d) << sh8);
-      Bw[k >> 2] = gt ? w : Bw[k >> 2];
+      T[k] = lanes_of(gtm) ? bt : T[k];
+      SetByteIf<k & 3, d>(Bw[k >> 2], gtm);
     };
     uint32_t next_start = 0;
     for (uint32_t p0 = 0; p0 <= nb; p0 += kU) {
       StaticFor<0, kU / kNI>([&](auto pc) {
         constexpr int jb = kNI * decltype(pc)::value;
         uint32_t pp[kNI], cl[kNI];
-        bool at[kNI], st[kNI], any[kNI];
+        uint32_t ucl = 0;  // byte q: position q's char length where its UNK node is not in the root table
+        bool at[kNI], st[kNI], any[kNI], unk_any[kNI];
         // Char starts in order (next_start chains through the group).
         StaticFor<0, kNI>([&](auto qc) {
           constexpr int q = decltype(qc)::value, j = jb + q;
@@ -434,6 +493,7 @@ void unigram_fast_kernel(FastArgs a) {
           at[q] = pp[q] <= nb && pp[q] == next_start;
           if (q == 0 && at[q] && pp[q] > 0) bp_store(pp[q], b_dist(std::integral_constant<int, j>{}));
           st[q] = at[q] && pp[q] < nb;
+          any[q] = (__builtin_amdgcn_ballot_w64(pp[q] == next_start) & __builtin_amdgcn_ballot_w64(pp[q] < nb)) != 0;
           cl[q] = OneCharLenDev(byte_of(std::integral_constant<int, j>{}));
           if (cl[q] > nb - pp[q]) cl[q] = nb - pp[q];
           if constexpr (kE) {
@@ -451,7 +511,12 @@ void unigram_fast_kernel(FastArgs a) {
             }
           }
           if (st[q]) next_start = pp[q] + cl[q];
-          any[q] = __builtin_amdgcn_ballot_w64(st[q]) != 0;
+          // The UNK node of a one-byte char is in the root table; the others
+          // (a multi-byte char, a stray tail byte) keep their select in the
+          // inserts of depth <= 4, skipped when no lane of the wave has one.
+          const uint32_t uq = st[q] && byte_of(std::integral_constant<int, j>{}) >= 0x80u ? cl[q] : 0u;
+          ucl |= uq << (8 * q);
+          unk_any[q] = __builtin_amdgcn_ballot_w64(uq != 0) != 0;
         });
         // Lagged inserts: position q's node of length dd is inserted at walk
         // step d = dd + 1 + q, right after the loads of step d are issued.
@@ -462,32 +527,26 @@ void unigram_fast_kernel(FastArgs a) {
         // (slot jb + q, final after step q + 1) are read at step q + 2,
         // before its first insert.
         float sok[kNI][W];  // node score of depth d (NaN: no usable node)
-        float T0q[kNI];
+        float T0q[kNI], Tbq[kNI];  // the position's own best score and its near-tie bound
         float A0q[kNI];
         int dm[kNI];
-        uint32_t bs[kNI], nd[kNI], c[kNI];
+        uint32_t off[kNI], c[kNI];  // off: byte offset of the walk's next (unit, score) pair
         UvT uv[kNI];
-        bool al[kNI];
         StaticFor<0, kNI>([&](auto qc) {
           constexpr int q = decltype(qc)::value;
           dm[q] = 0;
           T0q[q] = 0.f;
-          bs[q] = st[q] ? a.p.root_base : 0u;
-          al[q] = st[q];
+          Tbq[q] = 0.f;
         });
         bool go = any[0] || any[1];
         if (go) {
           StaticFor<0, kNI>([&](auto qc) {
             constexpr int q = decltype(qc)::value;
             c[q] = byte_of(std::integral_constant<int, jb + q>{});
-            if constexpr (kRootLds) {
-              const uint2 r = lds_root[c[q]];
-              uv[q][0] = r.x;
-              uv[q][1] = r.y;
-            } else {
-              nd[q] = bs[q] ^ c[q];
-              uv[q] = __builtin_amdgcn_raw_buffer_load_b64(uvs_rsrc, nd[q] * 8u, 0, 0);
-            }
+            // The root's child from LDS; entry 256 where no char starts.
+            const uint2 r = lds_root[st[q] ? c[q] : static_cast<uint32_t>(kBlock)];
+            uv[q][0] = r.x;
+            uv[q][1] = r.y;
           });
         }
         // Software pipeline: step d waits for the (unit, score) loads of
@@ -497,30 +556,42 @@ void unigram_fast_kernel(FastArgs a) {
         // node score: the walk is bound by the vector-memory address path
         // (TA busy 84 % of the kernel with separate unit and score gathers,
         // profiles/r03g_ta_unigram_fast.txt), so a step costs one gather.
+        // A lane whose walk has ended gathers pair 0, the root's own unit:
+        // its label is 0xFF (as every empty unit's), which no byte of an
+        // unflagged sentence matches, so the lane stays out without a flag
+        // of its own, and "alive" is one compare per step.
         StaticFor<1, W + kNI>([&](auto dc) {
           constexpr int d = decltype(dc)::value;
           if constexpr (d < W) {
             StaticFor<0, kNI>([&](auto qc) { sok[decltype(qc)::value][d] = __builtin_nanf(""); });
             if (go) {
-              bool g = false;
+              Mask alm[kNI];
               StaticFor<0, kNI>([&](auto qc) {
                 constexpr int q = decltype(qc)::value;
-                const uint32_t u = uv[q][0];
-                al[q] = al[q] && (u & 0xFFu) == c[q];
-                bs[q] = al[q] ? u >> 9 : 0u;
-                sok[q][d] = al[q] ? __uint_as_float(uv[q][1]) : __builtin_nanf("");
-                const bool gq = __builtin_amdgcn_ballot_w64(al[q]) != 0;
-                if (gq) dm[q] = d;
-                g = g || gq;
+                alm[q] = __builtin_amdgcn_ballot_w64((uv[q][0] & 0xFFu) == c[q]);
+                // (Depth 1: the root table's score is masked already.)
+                sok[q][d] = (d == 1 || lanes_of(alm[q])) ? __uint_as_float(uv[q][1]) : __builtin_nanf("");
+                if (alm[q] != 0) dm[q] = d;
               });
-              go = g;
+              go = (alm[0] | alm[1]) != 0;
               if constexpr (d + 1 < W) {
                 if (go) {
                   StaticFor<0, kNI>([&](auto qc) {
                     constexpr int q = decltype(qc)::value;
-                    c[q] = byte_of(std::integral_constant<int, jb + q + d>{});
-                    nd[q] = bs[q] ^ c[q];
-                    uv[q] = __builtin_amdgcn_raw_buffer_load_b64(uvs_rsrc, nd[q] * 8u, 0, 0);
+                    constexpr int t = jb + q + d;
+                    c[q] = byte_of(std::integral_constant<int, t>{});
+                    // 8 * (base ^ byte): byte t of the window at bits 3..10
+                    // (what lies below is masked off with the unit's flags).
+                    uint32_t c8;
+                    if constexpr ((t & 3) != 0) c8 = (rw[t >> 2] >> (8 * (t & 3) - 3)) & 0x7FFu;
+                    else c8 = (rw[t >> 2] & 0xFFu) << 3;
+                    off[q] = lanes_of(alm[q]) ? ((uv[q][0] >> 6) ^ c8) & ~7u : 0u;
+                    // The score is taken before the pair's registers are
+                    // loaded again (left to itself the compiler takes it
+                    // after, loads into a second register pair, and copies
+                    // that one back behind a wait ahead of the inserts).
+                    __asm__ volatile("" : "+v"(sok[q][d]), "+v"(off[q]));
+                    uv[q] = __builtin_amdgcn_raw_buffer_load_b64(uvs_rsrc, off[q], 0, 0);
                   });
                 }
               }
@@ -531,6 +602,7 @@ void unigram_fast_kernel(FastArgs a) {
             if constexpr (dd == 1) {
               if (q > 0 && at[q] && pp[q] > 0) bp_store(pp[q], b_dist(std::integral_constant<int, j>{}));
               T0q[q] = T[j];
+              Tbq[q] = TieBound(T0q[q], tie_mag);
               if constexpr (kE) {
                 // Slot j is final here: alpha of this char start (or Z at EOS).
                 A0q[q] = Ar[j];
@@ -546,7 +618,7 @@ void unigram_fast_kernel(FastArgs a) {
             if constexpr (dd >= 1 && dd < W) {
               if (any[q])
                 insert_one(std::integral_constant<int, j>{}, std::integral_constant<int, dd>{}, pp[q], T0q[q],
-                           kE ? A0q[q] : 0.f, cl[q], st[q], sok[q][dd], dm[q]);
+                           Tbq[q], kE ? A0q[q] : 0.f, (ucl >> (8 * q)) & 0xFFu, unk_any[q], sok[q][dd], dm[q]);
             }
           });
         });
@@ -561,6 +633,7 @@ void unigram_fast_kernel(FastArgs a) {
 #pragma unroll
       for (int m = 0; m < kBw; ++m) Bw[m] = m + 1 < kBw ? Bw[m + 1] : 0u;
       ambm >>= kU;
+      if (amb_wave) amb_wave = __builtin_amdgcn_ballot_w64(ambm != 0) != 0;
 #pragma unroll
       for (int k = 0; k + 1 < kWin; ++k) rw[k] = rw[k + 1];
       const uint32_t qn = p0 + kU + 4 * (kWin - 1);
@@ -871,8 +944,12 @@ void unigram_fast_kernel(FastArgs a) {
 
   // The lane's sentence index again, re-read from the permutation in LDS:
   // keeping the 64-bit index live across the walk cost a scratch spill.
+  // (So would the slot's LDS address: it is formed again from a thread index
+  // the compiler cannot match with the first one.)
   __asm__ volatile("" ::: "memory");
-  const uint32_t sid_e = lds_sort[kBlock + tid];
+  int tid_e = tid;
+  if constexpr (kByte) __asm__ volatile("" : "+v"(tid_e));
+  const uint32_t sid_e = lds_sort[kBlock + tid_e];
   const uint64_t ie = base + sid_e;
   const bool valid_e = ie < a.n;
   // Debug knob (spm_hip_model_set_debug_corrupt_bp): zero one sentence's EOS
