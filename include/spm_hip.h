@@ -150,6 +150,70 @@ int spm_hip_encode_batch_host(spm_hip_model *model, const uint8_t *norm_bytes,
                               const uint64_t *offsets, uint64_t n, int32_t *ids,
                               uint32_t *piece_len, uint64_t *tok_offsets);
 
+/* Batched SentencePieceProcessor::SampleEncode with nbest_size < 0
+ * (sentencepiece_processor.cc:622-659): one segmentation per sentence drawn
+ * from the unigram lattice (Lattice::Sample, unigram_model.cc:488-526) —
+ * subword regularization.  Buffers, blocking behaviour and outputs follow the
+ * contract of spm_hip_encode_batch.
+ *
+ * Lattice: that of Model::PopulateNodes (unigram_model.cc:535-604): positions
+ * are chars as SetSentence cuts them, UNUSED pieces are skipped, a
+ * USER_DEFINED piece scores length * max_score + 1, one UNK node of score
+ * min_score - 10 stands where no one-char piece matched, the trie walk stops
+ * at a NUL byte.
+ *
+ * Forward pass (all terms float): A[0] = 0 and, for each char position p,
+ *   A[p] = LogSumExp over nodes (b, p), in ascending b, of
+ *          fl(theta * score) + A[b],
+ * the first term initialising A[p]; LogSumExp is the reference's
+ * (unigram_model.cc:51-63: float storage, double exp / log, the 50 cutoff).
+ * This is Lattice::Sample's alpha, which depends on a node's begin position
+ * only.
+ *
+ * Backward pass, from e = len: the candidates are the nodes ending at e in
+ * ascending begin order (end_nodes_ insertion order, the longest piece
+ * first) with weights
+ *   w_i = (float) exp((double) fl(fl(A[b_i] + fl(theta * s_i)) - A[e])),
+ * S = w_0 + w_1 + .. summed in double in that order.  Draw u picks the first
+ * i with u < (w_0 + .. + w_i) / S, else the last candidate
+ * (std::discrete_distribution over probs).  The node becomes a token and
+ * e = b_i, until e = 0.  Tokens come out in sentence order; an empty
+ * sentence gives zero tokens.
+ *
+ * Random stream: stateless and counter based, so a result depends neither on
+ * the batch shape nor on the kernel that ran the sentence.  On uint64,
+ *   mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *           z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   sentence i of a call has global index g = index_base + i,
+ *   key = mix(seed + 0x9E3779B97F4A7C15 * (g + 1)),
+ *   draw k: u = (mix(key + 0x9E3779B97F4A7C15 * (k + 1)) >> 11) * 2^-53,
+ * k = 0 at EOS, counting up along the backward walk; no draw is spent once
+ * e = 0.  The reference seeds an mt19937 from random_device, which cannot be
+ * reproduced; what is kept is the distribution and the arithmetic above.
+ *
+ * Status: theta not finite -> SPM_INVALID_ARGUMENT.  A model that is not
+ * unigram -> SPM_UNIMPLEMENTED: the reference logs "Not implemented" and
+ * returns an empty result (model_interface.h:137-141), which over a C
+ * ABI would be indistinguishable from empty input.  A host-only handle ->
+ * SPM_FAILED_PRECONDITION.  spm_hip_model_last_stats reports general_path =
+ * the sentences the exact (literal lattice) kernel took: those the fast
+ * kernel cannot sample exactly (a piece of more than 64 bytes on the walk, a
+ * trie leaf inside a UTF-8 char, more than 16 nodes ending at one position),
+ * or all of them under spm_hip_model_set_force_general; both kernels run the
+ * same float operations in the same order and agree bit for bit. */
+int spm_hip_sample_encode_batch(spm_hip_model *model, const uint8_t *d_norm_bytes,
+                                const uint64_t *d_offsets, uint64_t n, float theta, uint64_t seed,
+                                uint64_t index_base, int32_t *d_ids, uint32_t *d_piece_len,
+                                uint64_t *d_tok_offsets, void *stream);
+/* Same contract with HOST buffers (offsets start at 0). */
+int spm_hip_sample_encode_batch_host(spm_hip_model *model, const uint8_t *norm_bytes,
+                                     const uint64_t *offsets, uint64_t n, float theta, uint64_t seed,
+                                     uint64_t index_base, int32_t *ids, uint32_t *piece_len,
+                                     uint64_t *tok_offsets);
+/* Host only: draw `draw` of the sentence with global index `index` under
+ * `seed`, the stream above (*u in [0, 1), a multiple of 2^-53). */
+int spm_hip_sample_uniform(uint64_t seed, uint64_t index, uint64_t draw, double *u);
+
 /* Normalizer::Normalize (normalizer.cc:88-211) on host threads, batched:
  * raw CSR lines in, normalized CSR out.  out capacity: 3*in_off[n] + 3*n
  * bytes.  norm_to_orig is not produced.  num_threads <= 0 → hardware

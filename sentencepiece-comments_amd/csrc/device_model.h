@@ -45,6 +45,7 @@ struct EncodeWorkspace {
   // Wave-cooperative kernel (coop_encode.hip): per-byte length masks and
   // chosen lnode lengths, and its list of sentences left to the general kernel.
   DevBuf w_cpv, w_cnd, w_crest, w_cpart;
+  DevBuf w_salpha, w_smask;  // sampler fast tier: alpha and node-distance mask per byte position
   DevBuf w_nlen, w_nscan;    // device normalizer: lengths, scan temp
   DevBuf w_ecount, w_escan;  // id epilogue: counts, scan temp
   DevBuf w_tids, w_tlen, w_ttok;  // SentencePieceText path: raw ids, piece lengths, token offsets

@@ -146,6 +146,74 @@ struct GeneralLaunch {
 };
 hipError_t LaunchUnigramGeneral(const UnigramLaunch &l, const GeneralLaunch &g, hipStream_t st);
 
+// Unigram SampleEncode (unigram_sample.hip): one segmentation per sentence
+// drawn from the lattice with theta-scaled scores (Lattice::Sample,
+// unigram_model.cc:488-526); draw k of sentence i comes from the stream of
+// sample_rng.h at global index index_base + i.  Both kernels write a
+// sentence's tokens right-aligned in its own byte range of slot_ids /
+// slot_len and the count to ntok[i] (the general kernel's contract);
+// LaunchCompact then packs them.
+//
+// Fast tier: one sentence per lane over all n sentences.  A / M: alpha and
+// the node-distance mask per byte position, capacity + n + 1 entries each
+// (position q of sentence i at off[i] + i + q; the launcher zeroes M).  A
+// sentence it cannot sample exactly is appended to `flagged`
+// (status[kStFlagged] counts, status[kStMaxNb] = the longest) for the exact
+// tier.  A batch beyond `capacity` sets bit 1 of status[kStError].
+struct SampleFastArgs {
+  const uint8_t *bytes;
+  const uint64_t *off;
+  uint64_t n;
+  uint64_t capacity;
+  const uint32_t *units;  // the plain double array
+  const int32_t *values;
+  const float *scores;
+  uint32_t num_units;
+  UnigramParams p;
+  float theta;
+  uint64_t seed;
+  uint64_t index_base;
+  float *A;
+  uint64_t *M;
+  int32_t *slot_ids;
+  uint32_t *slot_len;     // nullable
+  uint32_t *ntok;
+  uint32_t *flagged;      // n entries
+  uint32_t *status;       // kStWords
+};
+hipError_t LaunchUnigramSampleFast(const SampleFastArgs &a, hipStream_t st);
+
+// Exact tier: the literal lattice over a list of sentences (list == nullptr:
+// all list_n of them), slabs of UnigramGeneralSlabBytes as in GeneralLaunch;
+// sentences longer than max_nb go to ovf_list when it is set, else set bit 0
+// of *error.  A backward step that does not move left sets bit 2 of *error.
+struct SampleExactArgs {
+  const uint8_t *bytes;
+  const uint64_t *off;
+  const uint32_t *units;
+  const int32_t *values;
+  const float *scores;
+  uint32_t num_units;
+  UnigramParams p;
+  float theta;
+  uint64_t seed;
+  uint64_t index_base;
+  int32_t *slot_ids;
+  uint32_t *slot_len;
+  uint32_t *ntok;
+  const uint32_t *list;
+  const uint32_t *count;
+  uint64_t list_n;
+  uint8_t *scratch;
+  uint64_t slab_bytes;
+  uint32_t max_nb;
+  uint32_t *ovf_list;
+  uint32_t *ovf_count;
+  uint32_t *error;
+  uint32_t lanes;
+};
+hipError_t LaunchUnigramSampleExact(const SampleExactArgs &a, hipStream_t st);
+
 // Wave-cooperative encode (coop_encode.hip): one sentence per wavefront over a
 // device list (or all list_n sentences when list is null).  Output contract of
 // the general kernel: tokens right-aligned in slot_ids / slot_len of the

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <fstream>
 #include <iterator>
+#include <random>
 #include <sstream>
 
 namespace spm_amd {
@@ -285,9 +286,60 @@ Status SentencePieceProcessor::EncodeIdsSmall(const std::vector<std::string> &in
 Status SentencePieceProcessor::EncodeBatch(const std::vector<std::string> &inputs,
                                            std::vector<std::vector<int>> *ids,
                                            std::vector<std::vector<std::string>> *pieces) const {
+  return RunBatch(inputs, ids, pieces, nullptr);
+}
+
+void SentencePieceProcessor::SetRandomSeed(uint64_t seed) {
+  sample_seed_ = seed;
+  sample_count_ = 0;
+  sample_seeded_ = true;
+}
+
+Status SentencePieceProcessor::SampleEncodeBatch(const std::vector<std::string> &inputs, int nbest_size, float alpha,
+                                                 std::vector<std::vector<int>> *ids,
+                                                 std::vector<std::vector<std::string>> *pieces) const {
+  if (!status_.ok()) return status_;
+  if (nbest_size > 512) return Err(SPM_INTERNAL, "nbest_size must be nbest_size <= 512");
+  if (nbest_size == 0 || nbest_size == 1) return RunBatch(inputs, ids, pieces, nullptr);
+  if (nbest_size > 1)
+    return Err(SPM_UNIMPLEMENTED,
+               "SampleEncode among the n best (nbest_size > 1) is not implemented on the device; "
+               "use nbest_size=-1 to sample from the whole lattice");
+  if (!sample_seeded_) {
+    std::random_device rd;
+    sample_seed_ = (static_cast<uint64_t>(rd()) << 32) | rd();
+    sample_seeded_ = true;
+  }
+  const SampleSpec spec{alpha, sample_seed_, sample_count_};
+  Status st = RunBatch(inputs, ids, pieces, &spec);
+  if (st.ok()) sample_count_ += inputs.size();
+  return st;
+}
+
+Status SentencePieceProcessor::SampleEncode(const std::string &input, int nbest_size, float alpha,
+                                            std::vector<int> *ids) const {
+  if (!ids) return Err(SPM_INTERNAL, "output container is null");
+  std::vector<std::vector<int>> out;
+  Status st = SampleEncodeBatch({input}, nbest_size, alpha, &out, nullptr);
+  if (st.ok()) *ids = std::move(out[0]);
+  return st;
+}
+
+Status SentencePieceProcessor::SampleEncode(const std::string &input, int nbest_size, float alpha,
+                                            std::vector<std::string> *pieces) const {
+  if (!pieces) return Err(SPM_INTERNAL, "output container is null");
+  std::vector<std::vector<std::string>> out;
+  Status st = SampleEncodeBatch({input}, nbest_size, alpha, nullptr, &out);
+  if (st.ok()) *pieces = std::move(out[0]);
+  return st;
+}
+
+Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, std::vector<std::vector<int>> *ids,
+                                        std::vector<std::vector<std::string>> *pieces,
+                                        const SampleSpec *sample) const {
   if (!status_.ok()) return status_;
   const uint64_t n = inputs.size();
-  if (!pieces && ids && n >= 1 && n <= kSmallLines) {
+  if (!sample && !pieces && ids && n >= 1 && n <= kSmallLines) {
     uint64_t raw = 0;
     for (const auto &s : inputs) raw += s.size();
     if (raw <= kSmallBytes) {
@@ -331,7 +383,9 @@ Status SentencePieceProcessor::EncodeBatch(const std::vector<std::string> &input
   int32_t *d_ids = static_cast<int32_t *>(dev_.Get(kIds, std::max<uint64_t>(total, 1) * 4));
   uint32_t *d_len = static_cast<uint32_t *>(dev_.Get(kLen, std::max<uint64_t>(total, 1) * 4));
   if (!d_ids || !d_len) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
-  st = FromC(spm_hip_encode_batch(model_, d_norm, d_norm_off, n, d_ids, d_len, d_tok, nullptr));
+  st = FromC(sample ? spm_hip_sample_encode_batch(model_, d_norm, d_norm_off, n, sample->theta, sample->seed,
+                                                  sample->index_base, d_ids, d_len, d_tok, nullptr)
+                    : spm_hip_encode_batch(model_, d_norm, d_norm_off, n, d_ids, d_len, d_tok, nullptr));
   if (!st.ok()) return st;
   if (!pieces) {
     // Encode(ids): the id epilogue (unk-run merge + extra options) runs on the

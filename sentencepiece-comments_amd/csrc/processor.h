@@ -51,6 +51,26 @@ class SentencePieceProcessor {
   Status EncodeBatch(const std::vector<std::string> &inputs, std::vector<std::vector<int>> *ids,
                      std::vector<std::vector<std::string>> *pieces) const;
 
+  // SampleEncode (sentencepiece_processor.cc:622-659), batched.  nbest_size
+  // > 512 is an error; 0 or 1 is exactly Encode; < 0 draws one segmentation
+  // per line from the unigram lattice on the device with inverse temperature
+  // alpha (spm_hip_sample_encode_batch; a model that is not unigram gives
+  // SPM_UNIMPLEMENTED); > 1 (sampling among the n best) is SPM_UNIMPLEMENTED:
+  // there is no device NBest, use nbest_size = -1.  Unknown-run merge and the
+  // extra options apply as in Encode.  Line i of the k-th sampled call uses
+  // the random stream of global index (lines sampled so far) + i under the
+  // processor's seed, so repeated calls on one line give fresh draws and a
+  // fixed seed replays the whole sequence.
+  Status SampleEncode(const std::string &input, int nbest_size, float alpha, std::vector<int> *ids) const;
+  Status SampleEncode(const std::string &input, int nbest_size, float alpha,
+                      std::vector<std::string> *pieces) const;
+  Status SampleEncodeBatch(const std::vector<std::string> &inputs, int nbest_size, float alpha,
+                           std::vector<std::vector<int>> *ids,
+                           std::vector<std::vector<std::string>> *pieces) const;
+  // Seed of the sampler (default: from std::random_device); restarts the
+  // sentence counter.
+  void SetRandomSeed(uint64_t seed);
+
   int GetPieceSize() const;
   int PieceToId(const std::string &piece) const;
   const std::string &IdToPiece(int id) const;
@@ -71,6 +91,17 @@ class SentencePieceProcessor {
   std::vector<ExtraOption> extra_;
   std::string extra_str_;  // the accepted option string, for the device epilogue
   Status status_{SPM_INTERNAL, "Model is not initialized."};
+  // Sampler: the seed and the number of lines sampled so far (the next
+  // call's index_base).
+  mutable uint64_t sample_seed_ = 0, sample_count_ = 0;
+  mutable bool sample_seeded_ = false;
+  struct SampleSpec {
+    float theta;
+    uint64_t seed, index_base;
+  };
+  // EncodeBatch; with `sample` the device sampler stands in for the encode.
+  Status RunBatch(const std::vector<std::string> &inputs, std::vector<std::vector<int>> *ids,
+                  std::vector<std::vector<std::string>> *pieces, const SampleSpec *sample) const;
   // Grow-only device staging for EncodeBatch (raw lines → normalized → ids).
   struct Staging {
     void *ptr[10] = {};

@@ -1,5 +1,10 @@
 // spm_encode — drop-in for the reference CLI (src/spm_encode_main.cc:52-223)
-// for --output_format=id|piece, with batched device encoding.
+// for --output_format=id|piece|sample_id|sample_piece, with batched device
+// encoding.  sample_* is SampleEncode(line, --nbest_size, --alpha)
+// (spm_encode_main.cc:160-170): --nbest_size=-1 samples from the whole
+// lattice on the device, 0 or 1 is the plain encode; the reference's default
+// of 10 (sampling among the n best) has no device path and exits with a
+// message.  --random_seed (not in the reference) makes a run reproducible.
 //
 // The reference encodes one line at a time (spm_encode_main.cc:189-191).
 // Here lines are read in batches (--batch_lines), normalized and encoded on
@@ -22,15 +27,23 @@ namespace {
 struct Flags {
   std::string model, output_format = "piece", output, extra_options;
   long batch_lines = 1 << 20;
+  int nbest_size = 10;
+  float alpha = 0.5f;
+  bool has_seed = false;
+  unsigned long long random_seed = 0;
 };
 
 void Usage(const char *argv0) {
   std::cout << "Usage: " << argv0 << " [options] files\n\n"
             << "   --model (model file name)  type: string default: \n"
-            << "   --output_format (choose from piece or id)  type: string default: piece\n"
+            << "   --output_format (choose from piece, id, sample_piece or sample_id)  type: string default: piece\n"
             << "   --output (output filename)  type: string default: \n"
             << "   --extra_options (':' separated encoder extra options, e.g., "
                "\"reverse:bos:eos\")  type: string default: \n"
+            << "   --nbest_size (sample_*: -1 samples from the whole lattice, 0 or 1 is the best "
+               "segmentation; larger values are not implemented)  type: int32 default: 10\n"
+            << "   --alpha (smoothing parameter for sampling mode)  type: double default: 0.5\n"
+            << "   --random_seed (seed of the sampler; unset: random)  type: uint64 default: \n"
             << "   --batch_lines (lines per device batch)  type: int64 default: 1048576\n";
 }
 
@@ -87,6 +100,13 @@ int main(int argc, char **argv) {
       f.extra_options = v;
     } else if (k == "batch_lines") {
       f.batch_lines = std::max(1L, std::atol(v.c_str()));
+    } else if (k == "nbest_size") {
+      f.nbest_size = std::atoi(v.c_str());
+    } else if (k == "alpha") {
+      f.alpha = static_cast<float>(std::atof(v.c_str()));
+    } else if (k == "random_seed") {
+      f.has_seed = true;
+      f.random_seed = std::strtoull(v.c_str(), nullptr, 10);
     } else if (k == "minloglevel") {
     } else {
       Usage(argv[0]);
@@ -97,15 +117,18 @@ int main(int argc, char **argv) {
     Usage(argv[0]);
     Die("--model is required.");
   }
-  if (f.output_format != "id" && f.output_format != "piece")
+  const bool sample = f.output_format == "sample_id" || f.output_format == "sample_piece";
+  const bool want_ids = f.output_format == "id" || f.output_format == "sample_id";
+  if (!sample && f.output_format != "id" && f.output_format != "piece")
     Die("output_format \"" + f.output_format +
-        "\": only piece and id are implemented by the device engine");
+        "\": only piece, id, sample_piece and sample_id are implemented by the device engine");
 
   spm_amd::SentencePieceProcessor sp;
   auto st = sp.Load(f.model);
   if (!st.ok()) Die(st.message);
   st = sp.SetEncodeExtraOptions(f.extra_options);
   if (!st.ok()) Die(st.message);
+  if (f.has_seed) sp.SetRandomSeed(f.random_seed);
 
   std::ofstream ofs;
   std::ostream *out = &std::cout;
@@ -122,12 +145,13 @@ int main(int argc, char **argv) {
   std::string buf;
   auto flush = [&]() {
     if (batch.empty()) return;
-    auto s = f.output_format == "id" ? sp.EncodeBatch(batch, &ids, nullptr)
-                                     : sp.EncodeBatch(batch, nullptr, &pieces);
+    auto s = sample ? sp.SampleEncodeBatch(batch, f.nbest_size, f.alpha, want_ids ? &ids : nullptr,
+                                           want_ids ? nullptr : &pieces)
+                    : sp.EncodeBatch(batch, want_ids ? &ids : nullptr, want_ids ? nullptr : &pieces);
     if (!s.ok()) Die(s.message);
     for (size_t i = 0; i < batch.size(); ++i) {
       buf.clear();
-      if (f.output_format == "id") {
+      if (want_ids) {
         for (size_t k = 0; k < ids[i].size(); ++k) {
           if (k) buf += ' ';
           buf += std::to_string(ids[i][k]);

@@ -25,6 +25,7 @@
 #include "normalize_device.h"
 #include "normalizer.h"
 #include "piece_table.h"
+#include "sample_rng.h"
 #include "shard_plan.h"
 #include "trace.h"
 
@@ -855,7 +856,7 @@ void EncodeWorkspace::Release() {
   svc_prof = nullptr;
   for (DevBuf *b : {&w_ctl, &w_slot_ids, &w_slot_len, &w_tprefix, &w_slot2_ids, &w_slot2_len, &w_ntok, &w_cnt, &w_bp, &w_flagged, &w_ovf, &w_scan,
                     &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_tids, &w_tlen, &w_ttok,
-                    &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart})
+                    &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask})
     b->Release();
   if (pinned) (void)hipHostFree(pinned);
   pinned = nullptr;
@@ -2108,6 +2109,142 @@ int EncodeHostSmall(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_
   return SPM_OK;
 }
 
+// Blocking SampleEncode on a leased workspace: the fast tier over every
+// sentence, the exact tier over the sentences it flagged (device-count
+// passes, no-ops when none was), then scan + compaction.  force_general, or
+// a flagged sentence too long for the device pool, runs the exact tier over
+// every sentence with host-sized scratch.
+int SampleBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *d_bytes, const uint64_t *d_off,
+                   uint64_t n, float theta, uint64_t seed, uint64_t index_base, int32_t *d_ids, uint32_t *d_len,
+                   uint64_t *d_tok, hipStream_t st) {
+  uint64_t total = 0;
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 8, d_off + n, 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(&total, ws->pinned + 8, 8);
+  if (total > 0xFFFFFFFFull * 4) return Fail(SPM_OUT_OF_RANGE, "batch too large");
+  ws->stats = spm_hip_encode_stats{};
+  if (n == 0) {
+    SPM_HIP_TRY(hipMemsetAsync(d_tok, 0, sizeof(uint64_t), st));
+    SPM_HIP_TRY(hipStreamSynchronize(st));
+    spm_amd::PublishStats(m, ws->stats);
+    return SPM_OK;
+  }
+  const uint64_t cap = std::max<uint64_t>(total, 1);
+  const int K = m->up.trie_results_size;
+  SPM_HIP_TRY(ws->w_slot2_ids.Reserve(cap * 4));
+  if (d_len) SPM_HIP_TRY(ws->w_slot2_len.Reserve(cap * 4));
+  SPM_HIP_TRY(ws->w_ntok.Reserve(n * 4));
+  int32_t *s2 = ws->w_slot2_ids.as<int32_t>();
+  uint32_t *s2l = d_len ? ws->w_slot2_len.as<uint32_t>() : nullptr;
+  uint32_t *ntok = ws->w_ntok.as<uint32_t>();
+  const uint32_t num_units = static_cast<uint32_t>(m->trie.units.size());
+  bool host_sized = m->force_general;
+  uint32_t flagged = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    uint32_t *status = nullptr;
+    int rc = PrepareControl(ws, n, st, &status);
+    if (rc != SPM_OK) return rc;
+    spm_amd::SampleExactArgs x{d_bytes, d_off, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                               m->d_scores.as<float>(), num_units, m->up, theta, seed, index_base, s2, s2l, ntok};
+    x.error = status + spm_amd::kStError;
+    x.scratch = nullptr;
+    const bool timing = TimedSlot(m, ws) >= 0;
+    if (host_sized) {
+      uint32_t max_nb = 0;
+      rc = LongestSentence(d_off, n, st, &max_nb);
+      if (rc != SPM_OK) return rc;
+      max_nb = std::max<uint32_t>(max_nb, 1);
+      const uint64_t slab = spm_amd::UnigramGeneralSlabBytes(max_nb, K);
+      uint64_t threads = std::min<uint64_t>(n, 16384);
+      while (threads > 64 && threads * slab > (4ull << 30)) threads /= 2;
+      if (threads * slab > (16ull << 30)) return Fail(SPM_RESOURCE_EXHAUSTED, "sentence too long for the exact sampling path");
+      SPM_HIP_TRY(ws->w_scratch.Reserve(threads * slab));
+      x.list_n = n;
+      x.scratch = ws->w_scratch.as<uint8_t>();
+      x.slab_bytes = slab;
+      x.max_nb = max_nb;
+      x.lanes = static_cast<uint32_t>(threads);
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
+      SPM_HIP_TRY(spm_amd::LaunchUnigramSampleExact(x, st));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
+    } else {
+      SPM_HIP_TRY(ws->w_salpha.Reserve((cap + n + 1) * 4));
+      SPM_HIP_TRY(ws->w_smask.Reserve((cap + n + 1) * 8));
+      SPM_HIP_TRY(ws->w_flagged.Reserve(n * 4));
+      const auto gp = spm_amd::PlanGeneralPool(cap, kGeneralLanes, kGeneralSmallNb,
+                                               [&](uint32_t nb) { return spm_amd::UnigramGeneralSlabBytes(nb, K); });
+      SPM_HIP_TRY(ws->w_scratch.Reserve(gp.pool));
+      const uint64_t ovf_cap = std::min<uint64_t>(n, cap / (gp.small_nb + 1ull) + 1);
+      SPM_HIP_TRY(ws->w_ovf.Reserve(ovf_cap * 4));
+      spm_amd::SampleFastArgs f{d_bytes, d_off, n, total, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                                m->d_scores.as<float>(), num_units, m->up, theta, seed, index_base,
+                                ws->w_salpha.as<float>(), ws->w_smask.as<uint64_t>(), s2, s2l, ntok,
+                                ws->w_flagged.as<uint32_t>(), status};
+      const int slot = ws->last_slot;
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot], st));
+      SPM_HIP_TRY(spm_amd::LaunchUnigramSampleFast(f, st));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot + 1], st));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
+      // The flagged sentences: per-lane slabs first, the longer ones then
+      // one at a time with the whole pool.
+      x.list = ws->w_flagged.as<uint32_t>();
+      x.count = status + spm_amd::kStFlagged;
+      x.scratch = ws->w_scratch.as<uint8_t>();
+      x.slab_bytes = gp.slab;
+      x.max_nb = gp.small_nb;
+      x.lanes = gp.lanes;
+      x.ovf_list = ws->w_ovf.as<uint32_t>();
+      x.ovf_count = status + spm_amd::kStOverflow;
+      SPM_HIP_TRY(spm_amd::LaunchUnigramSampleExact(x, st));
+      x.list = ws->w_ovf.as<uint32_t>();
+      x.count = status + spm_amd::kStOverflow;
+      x.slab_bytes = gp.pool;
+      x.max_nb = gp.big_nb;
+      x.lanes = 1;
+      x.ovf_list = nullptr;
+      x.ovf_count = nullptr;
+      SPM_HIP_TRY(spm_amd::LaunchUnigramSampleExact(x, st));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
+    }
+    SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, status, 4 * (spm_amd::kStError + 1), hipMemcpyDeviceToHost, st));
+    SPM_HIP_TRY(hipStreamSynchronize(st));
+    flagged = ws->pinned[spm_amd::kStFlagged];
+    const uint32_t err = ws->pinned[spm_amd::kStError];
+    if (err == 0) {
+      size_t tmp = 0;
+      SPM_HIP_TRY(spm_amd::LaunchCompact(d_off, n, ntok, s2, s2l, d_ids, d_len, d_tok, nullptr, &tmp, status, nullptr,
+                                         st));
+      SPM_HIP_TRY(ws->w_scan.Reserve(tmp + 16));
+      SPM_HIP_TRY(spm_amd::LaunchCompact(d_off, n, ntok, s2, s2l, d_ids, d_len, d_tok, ws->w_scan.ptr, &tmp, status,
+                                         nullptr, st));
+      SPM_HIP_TRY(hipStreamSynchronize(st));
+      break;
+    }
+    // Bit 0: a flagged sentence outgrew the device pool; anything else is a
+    // broken walk, which a second run would only repeat.
+    if (host_sized || err != 1u) return Fail(SPM_INTERNAL, "exact sampling path: scratch overflow or broken walk");
+    host_sized = true;
+  }
+  ws->stats.sentences = n;
+  ws->stats.general_path = host_sized ? n : flagged;
+  if (m->timing && ws->last_slot >= 0) {
+    const int s = ws->last_slot;
+    if (!host_sized) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.fast_kernel_ms, ws->tev[2 * s], ws->tev[2 * s + 1]));
+    if (ws->stats.general_path) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
+    ws->tcount = 0;
+  }
+  spm_amd::PublishStats(m, ws->stats);
+  return SPM_OK;
+}
+
+int SampleArgsCheck(const spm_hip_model *m, float theta) {
+  if (!std::isfinite(theta)) return Fail(SPM_INVALID_ARGUMENT, "theta must be finite");
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  if (m->model_type != spm_amd::kUnigram)
+    return Fail(SPM_UNIMPLEMENTED, "SampleEncode is implemented for unigram models only");
+  return SPM_OK;
+}
+
 }  // namespace
 
 int spm_hip_encode_raw_small_host(spm_hip_model *m, const uint8_t *raw, const uint64_t *raw_off, uint64_t n,
@@ -2197,6 +2334,66 @@ int spm_hip_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint
   }
   ws->stats.tokens = ntok;
   spm_amd::PublishStats(m, ws->stats);
+  return SPM_OK;
+}
+
+int spm_hip_sample_encode_batch(spm_hip_model *m, const uint8_t *d_bytes, const uint64_t *d_off, uint64_t n,
+                                float theta, uint64_t seed, uint64_t index_base, int32_t *d_ids, uint32_t *d_len,
+                                uint64_t *d_tok, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_sample_encode_batch");
+  if (!m || (!d_off) || (!d_tok) || (n && !d_ids)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  const int rc = SampleArgsCheck(m, theta);
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForStream(m, st));
+  return SampleBlocking(m, ws.get(), d_bytes, d_off, n, theta, seed, index_base, d_ids, d_len, d_tok, st);
+}
+
+int spm_hip_sample_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                                     float theta, uint64_t seed, uint64_t index_base, int32_t *ids, uint32_t *len,
+                                     uint64_t *tok) {
+  spm_amd::TraceRange trace_range_("spm_hip_sample_encode_batch_host");
+  if (!m || !off || !tok) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  int rc = SampleArgsCheck(m, theta);
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  if (off[0] != 0) return Fail(SPM_INVALID_ARGUMENT, "offsets must start at 0");
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
+  const uint64_t total = off[n];
+  if (total && (!bytes || !ids)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForHost(m));
+  hipStream_t st = ws.stream();
+  SPM_HIP_TRY(ws->h_in.Reserve(std::max<uint64_t>(total, 1)));
+  SPM_HIP_TRY(ws->h_off.Reserve((n + 1) * 8));
+  SPM_HIP_TRY(ws->h_ids.Reserve(std::max<uint64_t>(total, 1) * 4));
+  if (len) SPM_HIP_TRY(ws->h_len.Reserve(std::max<uint64_t>(total, 1) * 4));
+  SPM_HIP_TRY(ws->h_tok.Reserve((n + 1) * 8));
+  if (total) SPM_HIP_TRY(hipMemcpyAsync(ws->h_in.ptr, bytes, total, hipMemcpyHostToDevice, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->h_off.ptr, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  rc = SampleBlocking(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), n, theta, seed, index_base,
+                      ws->h_ids.as<int32_t>(), len ? ws->h_len.as<uint32_t>() : nullptr, ws->h_tok.as<uint64_t>(),
+                      st);
+  if (rc != SPM_OK) return rc;
+  SPM_HIP_TRY(hipMemcpyAsync(tok, ws->h_tok.ptr, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t ntok = tok[n];
+  if (ntok) {
+    SPM_HIP_TRY(hipMemcpyAsync(ids, ws->h_ids.ptr, ntok * 4, hipMemcpyDeviceToHost, st));
+    if (len) SPM_HIP_TRY(hipMemcpyAsync(len, ws->h_len.ptr, ntok * 4, hipMemcpyDeviceToHost, st));
+    SPM_HIP_TRY(hipStreamSynchronize(st));
+  }
+  ws->stats.tokens = ntok;
+  spm_amd::PublishStats(m, ws->stats);
+  return SPM_OK;
+}
+
+int spm_hip_sample_uniform(uint64_t seed, uint64_t index, uint64_t draw, double *u) {
+  if (!u) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  *u = spm_amd::SampleDraw(spm_amd::SampleKey(seed, index), draw);
   return SPM_OK;
 }
 

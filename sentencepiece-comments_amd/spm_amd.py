@@ -41,6 +41,7 @@ EXPORTED = [
     "spm_hip_estep_record_stats", "spm_hip_estep_bucket_owner", "spm_hip_pieces_set_timing",
     "spm_hip_estep_kernel_times", "spm_hip_device_bytes", "spm_hip_device_peak_reset",
     "spm_hip_encode_raw_small_host", "spm_hip_model_piece_lookup",
+    "spm_hip_sample_encode_batch", "spm_hip_sample_encode_batch_host", "spm_hip_sample_uniform",
 ]
 
 ABI_VERSION = 3  # SPM_HIP_ABI_VERSION of include/spm_hip.h (struct layouts below)
@@ -194,6 +195,9 @@ def lib():
                                                  ctypes.POINTER(ctypes.c_float)]
         L.spm_hip_device_bytes.argtypes = [ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_encode_raw_small_host.argtypes = [P, P, P, U64, P, U64, P]
+        L.spm_hip_sample_encode_batch.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P, P]
+        L.spm_hip_sample_encode_batch_host.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P]
+        L.spm_hip_sample_uniform.argtypes = [U64, U64, U64, ctypes.POINTER(ctypes.c_double)]
         L.spm_hip_device_peak_reset.restype = None
         _lib = L
     return _lib
@@ -206,6 +210,15 @@ def _check(rc):
 
 def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def sample_uniform(seed, index, draw):
+    """Draw `draw` of the sentence with global index `index` under `seed`: the
+    sampler's counter-based stream (spm_hip_sample_uniform), u in [0, 1)."""
+    u = ctypes.c_double()
+    m = (1 << 64) - 1
+    _check(lib().spm_hip_sample_uniform(seed & m, index & m, draw & m, ctypes.byref(u)))
+    return u.value
 
 
 def to_csr(items):
@@ -417,6 +430,32 @@ class DeviceModel:
         if with_lens:
             return ids[:k], lens[:k], to
         return ids[:k], to
+
+    def sample_encode_csr_host(self, buf, off, theta, seed, index_base=0, with_lens=False):
+        """SampleEncode (nbest_size < 0) of host CSR sentences: one segmentation
+        per sentence drawn with inverse temperature theta; sentence i uses the
+        random stream of global index index_base + i under seed.  Returns what
+        encode_csr_host returns."""
+        n = len(off) - 1
+        cap = max(int(off[-1]), 1)
+        ids = np.zeros(cap, dtype=np.int32)
+        lens = np.zeros(cap, dtype=np.uint32) if with_lens else None
+        to = np.zeros(n + 1, dtype=np.uint64)
+        _check(self._L.spm_hip_sample_encode_batch_host(self.h, _p(buf), _p(off), n, theta, seed, index_base,
+                                                        _p(ids), _p(lens) if with_lens else None, _p(to)))
+        k = int(to[-1])
+        if with_lens:
+            return ids[:k], lens[:k], to
+        return ids[:k], to
+
+    def sample_encode_device(self, d_bytes, d_off, n, theta, seed, d_ids, d_tok, index_base=0, d_len=None,
+                             stream=None):
+        """spm_hip_sample_encode_batch on device pointers (ints); blocking."""
+        _check(self._L.spm_hip_sample_encode_batch(self.h, ctypes.c_void_p(d_bytes), ctypes.c_void_p(d_off), n,
+                                                   theta, seed, index_base, ctypes.c_void_p(d_ids),
+                                                   ctypes.c_void_p(d_len) if d_len else None,
+                                                   ctypes.c_void_p(d_tok),
+                                                   ctypes.c_void_p(stream) if stream else None))
 
     def encode_normalized(self, sentences):
         buf, off = to_csr(sentences)
