@@ -214,6 +214,85 @@ int spm_hip_sample_encode_batch_host(spm_hip_model *model, const uint8_t *norm_b
  * `seed`, the stream above (*u in [0, 1), a multiple of 2^-53). */
 int spm_hip_sample_uniform(uint64_t seed, uint64_t index, uint64_t draw, double *u);
 
+/* Batched unigram::Model::NBestEncode (unigram_model.cc:729-753 over
+ * Lattice::NBest :339-478): the nbest_size best segmentations of every
+ * sentence, DEVICE pointers.  Output is model level, like
+ * spm_hip_encode_batch: one UNK token per unknown char, no merge.
+ *
+ * Lattice: that of Model::PopulateNodes, as spelled out above for the
+ * sampler.  nbest_size is clamped to [1, 1024] (<= 0 counts as 1).
+ *
+ * N = 1: the Viterbi path, exactly what spm_hip_encode_batch returns.
+ * N >= 2: Viterbi first gives every node its backtrace_score (strict >, the
+ * first left node wins).  A* then runs from EOS over hypotheses (node, next,
+ * fx, gx), all float: a popped hypothesis pushes one child per node l ending
+ * at its node's position, in end_nodes_ insertion order, with
+ *   gx = fl(score[l] + gx_top),  fx = fl(backtrace_score[l] + gx_top).
+ * The agenda is a binary heap ordered by fx < and moved as libstdc++'s
+ * push_heap / pop_heap move a std::priority_queue, which decides the order of
+ * equal-fx hypotheses.  A popped BOS hypothesis is a result; the search ends
+ * at N results or with an empty agenda, so a lattice with fewer paths returns
+ * fewer.  When the agenda holds >= 100000 entries its top min(512, 10 N) are
+ * popped in order into a new agenda and the rest dropped.  A path's score is
+ * the float sum of its node scores in sentence order starting from 0.0f (it
+ * is not fx).  An empty sentence yields one path with no tokens and score 0.
+ *
+ * Output, a two-level CSR in sentence order (it depends neither on the batch
+ * shape nor on the tier that ran a sentence):
+ *   d_path_offsets : uint64[n + 1], sentence i owns paths
+ *                    [path_offsets[i], path_offsets[i + 1]), best first
+ *   d_tok_offsets  : uint64[path_capacity + 1], path p owns tokens
+ *                    [tok_offsets[p], tok_offsets[p + 1])
+ *   d_ids / d_piece_len (nullable) : token_capacity entries
+ *   d_scores       : float[path_capacity]
+ *   total_paths / total_tokens : HOST outputs (nullable)
+ * path_capacity = n * clamp(N) and token_capacity = clamp(N) * offsets[n]
+ * always suffice (at most N paths per sentence, at most one token per byte
+ * per path).  When a total exceeds its capacity the call returns
+ * SPM_RESOURCE_EXHAUSTED with both totals set and writes none of the five
+ * output arrays; a second call with the totals as capacities succeeds.
+ *
+ * Tiers: a first kernel launch gives every lane an arena of 40 N + 4 L + 64
+ * hypotheses (L = the longest sentence, at most 256 bytes); sentences that
+ * are longer or outgrow it run again with the same pool split among fewer
+ * lanes (16 times the arena); what still does not fit, and every search whose
+ * agenda reaches the 100000-entry shrink, is done on the host by the same
+ * search over the model's host tables.  All three agree bit for bit.  The
+ * host tier runs on one thread and moves each of its sentences separately: it
+ * is meant for the few that land there.
+ *
+ * Memory, kept by the stream's workspace until the model is freed or
+ * spm_hip_model_release_stream: search scratch up to 4 GiB, 8 n N bytes of
+ * per-path counts and scores, and token staging of N * offsets[n] entries
+ * (a third of that, then the exact need, beyond 32 M entries).
+ *
+ * BLOCKING, like spm_hip_encode_batch.  Status: a model that is not unigram
+ * -> SPM_UNIMPLEMENTED (the reference's model returns an empty result there,
+ * which the processor turns into INTERNAL; over a C ABI an empty result would
+ * be indistinguishable from empty input).  A host-only handle ->
+ * SPM_FAILED_PRECONDITION.  spm_hip_model_last_stats reports the call's
+ * sentences and tokens, general_path = sentences (every one runs the literal
+ * lattice) and, with timing on, general_kernel_ms = the two search launches. */
+int spm_hip_nbest_encode_batch(spm_hip_model *model, const uint8_t *d_norm_bytes,
+                               const uint64_t *d_offsets, uint64_t n, int32_t nbest_size,
+                               int32_t *d_ids, uint32_t *d_piece_len, uint64_t token_capacity,
+                               uint64_t *d_tok_offsets, float *d_scores, uint64_t path_capacity,
+                               uint64_t *d_path_offsets, uint64_t *total_paths,
+                               uint64_t *total_tokens, void *stream);
+/* Same contract with HOST buffers (offsets start at 0). */
+int spm_hip_nbest_encode_batch_host(spm_hip_model *model, const uint8_t *norm_bytes,
+                                    const uint64_t *offsets, uint64_t n, int32_t nbest_size,
+                                    int32_t *ids, uint32_t *piece_len, uint64_t token_capacity,
+                                    uint64_t *tok_offsets, float *scores, uint64_t path_capacity,
+                                    uint64_t *path_offsets, uint64_t *total_paths,
+                                    uint64_t *total_tokens);
+/* Testing knob: hypothesis arenas of the first and the second device tier
+ * (0 = automatic, the sizes above). */
+int spm_hip_model_set_nbest_max_hyps(spm_hip_model *model, uint32_t first, uint32_t second);
+/* Of the last n-best call on the handle: sentences the second device tier
+ * ran, and sentences the host ran. */
+int spm_hip_nbest_last_stats(const spm_hip_model *model, uint64_t *second_pass, uint64_t *host_path);
+
 /* Normalizer::Normalize (normalizer.cc:88-211) on host threads, batched:
  * raw CSR lines in, normalized CSR out.  out capacity: 3*in_off[n] + 3*n
  * bytes.  norm_to_orig is not produced.  num_threads <= 0 → hardware

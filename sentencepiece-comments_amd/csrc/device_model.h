@@ -46,6 +46,11 @@ struct EncodeWorkspace {
   // chosen lnode lengths, and its list of sentences left to the general kernel.
   DevBuf w_cpv, w_cnd, w_crest, w_cpart;
   DevBuf w_salpha, w_smask;  // sampler fast tier: alpha and node-distance mask per byte position
+  // NBestEncode: control words, per-sentence path counts and staging starts,
+  // per-path token counts and scores, token staging (device tiers / host
+  // tier), second-tier overflow list, offsets and gathered scores.
+  DevBuf w_nb_ctl, w_nb_npaths, w_nb_stage, w_nb_ntok, w_nb_score, w_nb_ids, w_nb_len, w_nb_hids, w_nb_hlen,
+      w_nb_ovf2, w_nb_poff, w_nb_ptok, w_nb_toff, w_nb_oscore;
   DevBuf w_nlen, w_nscan;    // device normalizer: lengths, scan temp
   DevBuf w_ecount, w_escan;  // id epilogue: counts, scan temp
   DevBuf w_tids, w_tlen, w_ttok;  // SentencePieceText path: raw ids, piece lengths, token offsets
@@ -132,6 +137,7 @@ struct spm_hip_model {
   std::vector<std::string> user_defined;
   spm_amd::DoubleArray trie;  // unigram: vocab trie; bpe: symbol trie
   spm_amd::UnigramParams up{};
+  std::vector<float> host_scores;  // unigram: score by piece id (the n-best host tier)
   int ring_width = 0;         // 16/32/64, 0 → general kernel only
   spm_amd::UnigramKernel kernel = spm_amd::UnigramKernel::kGeneralOnly;
   std::atomic<bool> force_general{false};
@@ -167,6 +173,8 @@ struct spm_hip_model {
   uint64_t use_clock = 0;  // LRU stamps of by_stream
   std::vector<std::unique_ptr<spm_amd::EncodeWorkspace>> host_pool;
   spm_hip_encode_stats last_stats{};  // of the last completed encode call (pool_mu)
+  uint64_t nbest_second = 0, nbest_host = 0;  // of the last n-best call (pool_mu)
+  std::atomic<uint32_t> nbest_hyps1{0}, nbest_hyps2{0};  // spm_hip_model_set_nbest_max_hyps
   int device = 0;
 };
 

@@ -214,6 +214,76 @@ struct SampleExactArgs {
 };
 hipError_t LaunchUnigramSampleExact(const SampleExactArgs &a, hipStream_t st);
 
+// Unigram NBestEncode (unigram_nbest.hip): the n best segmentations of every
+// sentence (Lattice::NBest, unigram_model.cc:339-478), one sentence per lane
+// over a list (list == nullptr: all list_n sentences).  Per-lane slabs of
+// UnigramNBestSlabBytes(max_nb, K, max_hyps).  A sentence longer than max_nb,
+// or whose search needs more than max_hyps hypotheses or reaches the
+// reference's agenda shrink, is appended to ovf_list and writes nothing.
+// Every other sentence i writes npaths[i], the token count and score of its
+// path k at [i * nbest + k], and its paths' tokens one after the other from
+// staging entry stage[i], claimed from *stage_cursor; when the claim ends
+// beyond stage_cap the tokens are not written (the cursor tells the host how
+// much staging the call needs).
+constexpr uint64_t kNBestHostStage = 1ull << 63;  // stage[i]: the block is in the host tier's staging
+struct NBestLaunch {
+  const uint8_t *bytes;
+  const uint64_t *off;
+  const uint32_t *units;  // the plain double array
+  const int32_t *values;
+  const float *scores;
+  uint32_t num_units;
+  UnigramParams p;
+  int32_t nbest;          // clamped to [1, 1024]
+  const uint32_t *list;
+  const uint32_t *count;
+  uint64_t list_n;
+  uint8_t *scratch;
+  uint64_t slab_bytes;
+  uint32_t max_nb;
+  uint32_t max_hyps;
+  uint32_t lanes;
+  uint32_t *ovf_list;     // n entries
+  uint32_t *ovf_count;
+  uint32_t *npaths;       // n
+  uint64_t *stage;        // n
+  uint32_t *path_ntok;    // n * nbest
+  float *path_score;      // n * nbest
+  int32_t *stage_ids;     // stage_cap
+  uint32_t *stage_len;    // nullable
+  uint64_t stage_cap;
+  unsigned long long *stage_cursor;
+};
+uint64_t UnigramNBestSlabBytes(uint32_t max_nb, int trie_results_size, uint32_t max_hyps);
+hipError_t LaunchUnigramNBest(const NBestLaunch &a, hipStream_t st);
+// path_off[n + 1] = scan of npaths (tmp == nullptr: the scan's scratch size).
+hipError_t LaunchNBestPathOffsets(const uint32_t *npaths, uint64_t n, uint64_t *path_off, void *tmp,
+                                  size_t *tmp_bytes, hipStream_t st);
+// ptok[total_paths] = the paths' token counts in output order and
+// tok_off[total_paths + 1] their scan (tmp == nullptr: the scratch size).
+hipError_t LaunchNBestTokOffsets(uint64_t n, uint32_t nbest, const uint32_t *npaths, const uint64_t *path_off,
+                                 const uint32_t *path_ntok, uint64_t total_paths, uint32_t *ptok, uint64_t *tok_off,
+                                 void *tmp, size_t *tmp_bytes, hipStream_t st);
+// Every sentence's staged block (device staging, or the host tier's when
+// stage[i] carries kNBestHostStage) to its place in ids / piece_len, and its
+// paths' scores to scores.
+struct NBestGather {
+  uint64_t n;
+  uint32_t nbest;
+  const uint64_t *path_off;
+  const uint64_t *tok_off;
+  const uint64_t *stage;
+  const float *path_score;
+  const int32_t *stage_ids;
+  const uint32_t *stage_len;
+  const int32_t *host_ids;
+  const uint32_t *host_len;
+  int32_t *ids;
+  uint32_t *piece_len;    // nullable
+  float *scores;
+};
+hipError_t LaunchNBestGather(const NBestGather &g, hipStream_t st);
+
 // Wave-cooperative encode (coop_encode.hip): one sentence per wavefront over a
 // device list (or all list_n sentences when list is null).  Output contract of
 // the general kernel: tokens right-aligned in slot_ids / slot_len of the

@@ -426,43 +426,208 @@ Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, 
     return fail_hip(he);
   if (ids) ids->assign(n, {});
   if (pieces) pieces->assign(n, {});
-  const std::string &bos = proto_.trainer_spec.bos_piece, &eos = proto_.trainer_spec.eos_piece;
   std::vector<std::pair<std::string, int>> spt;
   for (uint64_t i = 0; i < n; ++i) {
-    // PopulateSentencePieceText (sentencepiece_processor.cc:488-551).
-    spt.clear();
     const char *normalized = pieces ? reinterpret_cast<const char *>(norm.data()) + norm_off[i] : nullptr;
-    const uint64_t nlen = norm_off[i + 1] - norm_off[i];
-    uint64_t consumed = 0;
-    bool prev_unk = false;
-    for (uint64_t k = tok_off[i]; k < tok_off[i + 1]; ++k) {
-      const int id = tok_ids[k];
-      const uint32_t len = tok_len[k];
-      if (len == 0) return Err(SPM_INTERNAL, "Empty piece is not allowed.");
-      std::string w = normalized ? std::string(normalized + consumed, len) : std::string();
-      const bool is_unk = IsUnknown(id);
-      if (IsControl(id)) {
-        spt.emplace_back(std::move(w), id);
-      } else {
-        if (prev_unk && is_unk) spt.back().first += w;
-        else spt.emplace_back(std::move(w), id);
-        consumed += len;
-      }
-      prev_unk = is_unk;
-    }
-    if (consumed != nlen) return Err(SPM_INTERNAL, "all normalized characters are not consumed.");
-    // ApplyExtraOptions (sentencepiece_processor.cc:945-979).
-    for (ExtraOption opt : extra_) {
-      if (opt == REVERSE) std::reverse(spt.begin(), spt.end());
-      else if (opt == EOS) spt.emplace_back(eos, PieceToId(eos));
-      else spt.insert(spt.begin(), {bos, PieceToId(bos)});
-    }
+    Status ps = PopulateText(normalized, norm_off[i + 1] - norm_off[i], tok_ids.data() + tok_off[i],
+                             tok_len.data() + tok_off[i], tok_off[i + 1] - tok_off[i], &spt);
+    if (!ps.ok()) return ps;
     if (ids)
       for (auto &p : spt) (*ids)[i].push_back(p.second);
     if (pieces)
       for (auto &p : spt) (*pieces)[i].push_back(std::move(p.first));
   }
   return Status::Ok();
+}
+
+// PopulateSentencePieceText (sentencepiece_processor.cc:488-551) +
+// ApplyExtraOptions (:945-979) over one path's model-level tokens: (piece,
+// id) pairs with unknown runs merged.  normalized == nullptr: ids only.
+Status SentencePieceProcessor::PopulateText(const char *normalized, uint64_t nlen, const int32_t *tok_ids,
+                                            const uint32_t *tok_len, uint64_t count,
+                                            std::vector<std::pair<std::string, int>> *out) const {
+  std::vector<std::pair<std::string, int>> &spt = *out;
+  spt.clear();
+  uint64_t consumed = 0;
+  bool prev_unk = false;
+  for (uint64_t k = 0; k < count; ++k) {
+    const int id = tok_ids[k];
+    const uint32_t len = tok_len[k];
+    if (len == 0) return Err(SPM_INTERNAL, "Empty piece is not allowed.");
+    std::string w = normalized ? std::string(normalized + consumed, len) : std::string();
+    const bool is_unk = IsUnknown(id);
+    if (IsControl(id)) {
+      spt.emplace_back(std::move(w), id);
+    } else {
+      if (prev_unk && is_unk) spt.back().first += w;
+      else spt.emplace_back(std::move(w), id);
+      consumed += len;
+    }
+    prev_unk = is_unk;
+  }
+  if (consumed != nlen) return Err(SPM_INTERNAL, "all normalized characters are not consumed.");
+  const std::string &bos = proto_.trainer_spec.bos_piece, &eos = proto_.trainer_spec.eos_piece;
+  for (ExtraOption opt : extra_) {
+    if (opt == REVERSE) std::reverse(spt.begin(), spt.end());
+    else if (opt == EOS) spt.emplace_back(eos, PieceToId(eos));
+    else spt.insert(spt.begin(), {bos, PieceToId(bos)});
+  }
+  return Status::Ok();
+}
+
+// NBestEncode (sentencepiece_processor.cc:588-609), batched: the device
+// normalizer, spm_hip_nbest_encode_batch over the chunk, then
+// PopulateSentencePieceText on every path.  Ids alone finish on the device
+// (spm_hip_finalize_ids with every path passed as a "sentence"); pieces and
+// scores are put together on the host.
+Status SentencePieceProcessor::NBestEncodeBatch(const std::vector<std::string> &inputs, int nbest_size,
+                                                std::vector<std::vector<std::vector<int>>> *ids,
+                                                std::vector<std::vector<std::vector<std::string>>> *pieces,
+                                                std::vector<std::vector<float>> *scores) const {
+  if (!status_.ok()) return status_;
+  // The reference's non-unigram models return no path at all (:598-599).
+  if (proto_.trainer_spec.model_type != kUnigram) return Err(SPM_INTERNAL, "NBestEncode returns empty result.");
+  const uint64_t n_all = inputs.size();
+  const uint64_t N = static_cast<uint64_t>(std::max(1, std::min(nbest_size, 1024)));
+  if (ids) ids->assign(n_all, {});
+  if (pieces) pieces->assign(n_all, {});
+  if (scores) scores->assign(n_all, {});
+  // Chunks of at most 2^20 paths and 2^26 path bytes, so staging stays bounded.
+  const uint64_t max_lines = std::max<uint64_t>(1, (1ull << 20) / N);
+  const uint64_t max_bytes = std::max<uint64_t>(1, (1ull << 26) / N);
+  enum { kIn, kInOff, kNorm, kNormOff, kIds, kLen, kTok, kOut, kOutOff, kSmallBlock };
+  // (kSmallBlock doubles as the path-level arrays: EncodeIdsSmall is not running.)
+  auto fail_hip = [](hipError_t e) { return Err(SPM_INTERNAL, hipGetErrorString(e)); };
+  hipError_t he;
+  std::vector<std::pair<std::string, int>> spt;
+  for (uint64_t c0 = 0; c0 < n_all;) {
+    uint64_t c1 = c0, raw = 0;
+    while (c1 < n_all && c1 - c0 < max_lines && (c1 == c0 || raw + inputs[c1].size() <= max_bytes))
+      raw += inputs[c1++].size();
+    const uint64_t n = c1 - c0;
+    std::vector<uint64_t> in_off(n + 1, 0);
+    std::string in_bytes;
+    in_bytes.reserve(raw);
+    for (uint64_t i = 0; i < n; ++i) {
+      in_bytes += inputs[c0 + i];
+      in_off[i + 1] = in_bytes.size();
+    }
+    uint8_t *d_in = static_cast<uint8_t *>(dev_.Get(kIn, std::max<uint64_t>(raw, 1)));
+    uint64_t *d_in_off = static_cast<uint64_t *>(dev_.Get(kInOff, (n + 1) * 8));
+    uint64_t *d_norm_off = static_cast<uint64_t *>(dev_.Get(kNormOff, (n + 1) * 8));
+    uint64_t *d_path_off = static_cast<uint64_t *>(dev_.Get(kOutOff, (n + 1) * 8));
+    if (!d_in || !d_in_off || !d_norm_off || !d_path_off)
+      return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+    if ((raw && (he = hipMemcpy(d_in, in_bytes.data(), raw, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (he = hipMemcpy(d_in_off, in_off.data(), (n + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess)
+      return fail_hip(he);
+    uint64_t total = 0;
+    uint8_t *d_norm = static_cast<uint8_t *>(dev_.Get(kNorm, std::max<uint64_t>(dev_.cap[kNorm], 1)));
+    int rc = spm_hip_normalize_batch_device(model_, d_in, d_in_off, n, d_norm, dev_.cap[kNorm], d_norm_off, &total,
+                                            nullptr);
+    if (rc == SPM_RESOURCE_EXHAUSTED) {
+      d_norm = static_cast<uint8_t *>(dev_.Get(kNorm, total));
+      if (!d_norm) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+      rc = spm_hip_normalize_batch_device(model_, d_in, d_in_off, n, d_norm, dev_.cap[kNorm], d_norm_off, &total,
+                                          nullptr);
+    }
+    Status st = FromC(rc);
+    if (!st.ok()) return st;
+    // First try: capacities for 16 tokens per path, then the returned totals.
+    uint64_t P = n * N, T = std::min<uint64_t>(std::max<uint64_t>(total, 1) * N, n * N * 16 + 1024);
+    int32_t *d_ids = nullptr;
+    uint32_t *d_len = nullptr;
+    uint64_t *d_tok = nullptr;
+    float *d_scores = nullptr;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      d_ids = static_cast<int32_t *>(dev_.Get(kIds, std::max<uint64_t>(T, 1) * 4));
+      d_len = static_cast<uint32_t *>(dev_.Get(kLen, std::max<uint64_t>(T, 1) * 4));
+      d_tok = static_cast<uint64_t *>(dev_.Get(kTok, (P + 1) * 8));
+      d_scores = static_cast<float *>(dev_.Get(kSmallBlock, std::max<uint64_t>(P, 1) * 4));
+      if (!d_ids || !d_len || !d_tok || !d_scores) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+      const uint64_t pcap = P, tcap = T;
+      rc = spm_hip_nbest_encode_batch(model_, d_norm, d_norm_off, n, static_cast<int32_t>(N), d_ids, d_len, tcap, d_tok,
+                                      d_scores, pcap, d_path_off, &P, &T, nullptr);
+      if (rc != SPM_RESOURCE_EXHAUSTED) break;
+    }
+    st = FromC(rc);
+    if (!st.ok()) return st;
+    std::vector<uint64_t> path_off(n + 1);
+    if ((he = hipMemcpy(path_off.data(), d_path_off, (n + 1) * 8, hipMemcpyDeviceToHost)) != hipSuccess)
+      return fail_hip(he);
+    if (scores) {
+      std::vector<float> sc(std::max<uint64_t>(P, 1));
+      if (P && (he = hipMemcpy(sc.data(), d_scores, P * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(he);
+      for (uint64_t i = 0; i < n; ++i) (*scores)[c0 + i].assign(sc.begin() + path_off[i], sc.begin() + path_off[i + 1]);
+    }
+    if (!pieces) {
+      if (ids) {
+        uint64_t n_extra = 0;
+        for (ExtraOption opt : extra_) n_extra += opt != REVERSE;
+        const uint64_t cap = T + P * n_extra;
+        uint64_t *d_out_off = static_cast<uint64_t *>(dev_.Get(kInOff, (P + 1) * 8));
+        int32_t *d_out = static_cast<int32_t *>(dev_.Get(kOut, std::max<uint64_t>(cap, 1) * 4));
+        if (!d_out_off || !d_out) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+        uint64_t fin = 0;
+        st = FromC(spm_hip_finalize_ids(model_, extra_str_.c_str(), d_ids, d_tok, P, d_out, cap, d_out_off, &fin,
+                                        nullptr));
+        if (!st.ok()) return st;
+        std::vector<uint64_t> out_off(P + 1);
+        std::vector<int32_t> out(std::max<uint64_t>(fin, 1));
+        if ((he = hipMemcpy(out_off.data(), d_out_off, (P + 1) * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
+            (fin && (he = hipMemcpy(out.data(), d_out, fin * 4, hipMemcpyDeviceToHost)) != hipSuccess))
+          return fail_hip(he);
+        for (uint64_t i = 0; i < n; ++i)
+          for (uint64_t p = path_off[i]; p < path_off[i + 1]; ++p)
+            (*ids)[c0 + i].emplace_back(out.begin() + out_off[p], out.begin() + out_off[p + 1]);
+      }
+      c0 = c1;
+      continue;
+    }
+    std::vector<uint64_t> norm_off(n + 1), tok_off(P + 1);
+    std::vector<int32_t> tok_ids(std::max<uint64_t>(T, 1));
+    std::vector<uint32_t> tok_len(std::max<uint64_t>(T, 1));
+    std::vector<uint8_t> norm(std::max<uint64_t>(total, 1));
+    if ((he = hipMemcpy(norm_off.data(), d_norm_off, (n + 1) * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
+        (he = hipMemcpy(tok_off.data(), d_tok, (P + 1) * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
+        (T && (he = hipMemcpy(tok_ids.data(), d_ids, T * 4, hipMemcpyDeviceToHost)) != hipSuccess) ||
+        (T && (he = hipMemcpy(tok_len.data(), d_len, T * 4, hipMemcpyDeviceToHost)) != hipSuccess) ||
+        (total && (he = hipMemcpy(norm.data(), d_norm, total, hipMemcpyDeviceToHost)) != hipSuccess))
+      return fail_hip(he);
+    for (uint64_t i = 0; i < n; ++i)
+      for (uint64_t p = path_off[i]; p < path_off[i + 1]; ++p) {
+        const char *normalized = reinterpret_cast<const char *>(norm.data()) + norm_off[i];
+        Status ps = PopulateText(normalized, norm_off[i + 1] - norm_off[i], tok_ids.data() + tok_off[p],
+                                 tok_len.data() + tok_off[p], tok_off[p + 1] - tok_off[p], &spt);
+        if (!ps.ok()) return ps;
+        if (ids) {
+          (*ids)[c0 + i].emplace_back();
+          for (auto &q : spt) (*ids)[c0 + i].back().push_back(q.second);
+        }
+        (*pieces)[c0 + i].emplace_back();
+        for (auto &q : spt) (*pieces)[c0 + i].back().push_back(std::move(q.first));
+      }
+    c0 = c1;
+  }
+  return Status::Ok();
+}
+
+Status SentencePieceProcessor::NBestEncode(const std::string &input, int nbest_size,
+                                           std::vector<std::vector<int>> *ids) const {
+  if (!ids) return Err(SPM_INTERNAL, "output container is null");
+  std::vector<std::vector<std::vector<int>>> out;
+  Status st = NBestEncodeBatch({input}, nbest_size, &out, nullptr, nullptr);
+  if (st.ok()) *ids = std::move(out[0]);
+  return st;
+}
+
+Status SentencePieceProcessor::NBestEncode(const std::string &input, int nbest_size,
+                                           std::vector<std::vector<std::string>> *pieces) const {
+  if (!pieces) return Err(SPM_INTERNAL, "output container is null");
+  std::vector<std::vector<std::vector<std::string>>> out;
+  Status st = NBestEncodeBatch({input}, nbest_size, nullptr, &out, nullptr);
+  if (st.ok()) *pieces = std::move(out[0]);
+  return st;
 }
 
 Status SentencePieceProcessor::Encode(const std::string &input, std::vector<int> *ids) const {

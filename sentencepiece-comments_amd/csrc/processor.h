@@ -56,7 +56,8 @@ class SentencePieceProcessor {
   // per line from the unigram lattice on the device with inverse temperature
   // alpha (spm_hip_sample_encode_batch; a model that is not unigram gives
   // SPM_UNIMPLEMENTED); > 1 (sampling among the n best) is SPM_UNIMPLEMENTED:
-  // there is no device NBest, use nbest_size = -1.  Unknown-run merge and the
+  // use nbest_size = -1 (NBestEncode below returns the n best themselves).
+  // Unknown-run merge and the
   // extra options apply as in Encode.  Line i of the k-th sampled call uses
   // the random stream of global index (lines sampled so far) + i under the
   // processor's seed, so repeated calls on one line give fresh draws and a
@@ -70,6 +71,20 @@ class SentencePieceProcessor {
   // Seed of the sampler (default: from std::random_device); restarts the
   // sentence counter.
   void SetRandomSeed(uint64_t seed);
+
+  // NBestEncode (sentencepiece_processor.cc:588-609), batched: the nbest_size
+  // (clamped to [1, 1024]) best segmentations of every line, best first, from
+  // the device A* search (spm_hip_nbest_encode_batch); a line with fewer
+  // paths returns fewer.  Unknown-run merge and the extra options apply to
+  // every path.  scores: the paths' model scores.  Each output may be null.
+  // A model that is not unigram gives INTERNAL "NBestEncode returns empty
+  // result.", as the reference does.  Large batches run in chunks.
+  Status NBestEncode(const std::string &input, int nbest_size, std::vector<std::vector<int>> *ids) const;
+  Status NBestEncode(const std::string &input, int nbest_size, std::vector<std::vector<std::string>> *pieces) const;
+  Status NBestEncodeBatch(const std::vector<std::string> &inputs, int nbest_size,
+                          std::vector<std::vector<std::vector<int>>> *ids,
+                          std::vector<std::vector<std::vector<std::string>>> *pieces,
+                          std::vector<std::vector<float>> *scores) const;
 
   int GetPieceSize() const;
   int PieceToId(const std::string &piece) const;
@@ -102,6 +117,9 @@ class SentencePieceProcessor {
   // EncodeBatch; with `sample` the device sampler stands in for the encode.
   Status RunBatch(const std::vector<std::string> &inputs, std::vector<std::vector<int>> *ids,
                   std::vector<std::vector<std::string>> *pieces, const SampleSpec *sample) const;
+  // PopulateSentencePieceText + ApplyExtraOptions over one path's tokens.
+  Status PopulateText(const char *normalized, uint64_t nlen, const int32_t *tok_ids, const uint32_t *tok_len,
+                      uint64_t count, std::vector<std::pair<std::string, int>> *out) const;
   // Grow-only device staging for EncodeBatch (raw lines → normalized → ids).
   struct Staging {
     void *ptr[10] = {};

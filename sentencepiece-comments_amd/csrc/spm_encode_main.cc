@@ -1,10 +1,13 @@
 // spm_encode — drop-in for the reference CLI (src/spm_encode_main.cc:52-223)
-// for --output_format=id|piece|sample_id|sample_piece, with batched device
-// encoding.  sample_* is SampleEncode(line, --nbest_size, --alpha)
-// (spm_encode_main.cc:160-170): --nbest_size=-1 samples from the whole
-// lattice on the device, 0 or 1 is the plain encode; the reference's default
-// of 10 (sampling among the n best) has no device path and exits with a
-// message.  --random_seed (not in the reference) makes a run reproducible.
+// for --output_format=id|piece|sample_id|sample_piece|nbest_id|nbest_piece,
+// with batched device encoding.  sample_* is SampleEncode(line, --nbest_size,
+// --alpha) (spm_encode_main.cc:133-144): --nbest_size=-1 samples from the
+// whole lattice on the device, 0 or 1 is the plain encode; the reference's
+// default of 10 (sampling among the n best) is not implemented and exits
+// with a message.  nbest_* is NBestEncode(line, --nbest_size)
+// (spm_encode_main.cc:154-169): one output line per path of every input
+// line, best first.  --random_seed (not in the reference) makes a run
+// reproducible.
 //
 // The reference encodes one line at a time (spm_encode_main.cc:189-191).
 // Here lines are read in batches (--batch_lines), normalized and encoded on
@@ -36,12 +39,14 @@ struct Flags {
 void Usage(const char *argv0) {
   std::cout << "Usage: " << argv0 << " [options] files\n\n"
             << "   --model (model file name)  type: string default: \n"
-            << "   --output_format (choose from piece, id, sample_piece or sample_id)  type: string default: piece\n"
+            << "   --output_format (choose from piece, id, sample_piece, sample_id, nbest_piece or nbest_id)  "
+               "type: string default: piece\n"
             << "   --output (output filename)  type: string default: \n"
             << "   --extra_options (':' separated encoder extra options, e.g., "
                "\"reverse:bos:eos\")  type: string default: \n"
-            << "   --nbest_size (sample_*: -1 samples from the whole lattice, 0 or 1 is the best "
-               "segmentation; larger values are not implemented)  type: int32 default: 10\n"
+            << "   --nbest_size (nbest_*: number of segmentations per line; sample_*: -1 samples from the "
+               "whole lattice, 0 or 1 is the best segmentation, larger values are not implemented)  "
+               "type: int32 default: 10\n"
             << "   --alpha (smoothing parameter for sampling mode)  type: double default: 0.5\n"
             << "   --random_seed (seed of the sampler; unset: random)  type: uint64 default: \n"
             << "   --batch_lines (lines per device batch)  type: int64 default: 1048576\n";
@@ -118,10 +123,12 @@ int main(int argc, char **argv) {
     Die("--model is required.");
   }
   const bool sample = f.output_format == "sample_id" || f.output_format == "sample_piece";
-  const bool want_ids = f.output_format == "id" || f.output_format == "sample_id";
-  if (!sample && f.output_format != "id" && f.output_format != "piece")
+  const bool nbest = f.output_format == "nbest_id" || f.output_format == "nbest_piece";
+  const bool want_ids = f.output_format == "id" || f.output_format == "sample_id" || f.output_format == "nbest_id";
+  if (!sample && !nbest && f.output_format != "id" && f.output_format != "piece")
     Die("output_format \"" + f.output_format +
-        "\": only piece, id, sample_piece and sample_id are implemented by the device engine");
+        "\": only piece, id, sample_piece, sample_id, nbest_piece and nbest_id are implemented by the device "
+        "engine");
 
   spm_amd::SentencePieceProcessor sp;
   auto st = sp.Load(f.model);
@@ -142,9 +149,37 @@ int main(int argc, char **argv) {
   std::vector<std::string> batch;
   std::vector<std::vector<int>> ids;
   std::vector<std::vector<std::string>> pieces;
+  std::vector<std::vector<std::vector<int>>> nbest_ids;
+  std::vector<std::vector<std::vector<std::string>>> nbest_pieces;
   std::string buf;
   auto flush = [&]() {
     if (batch.empty()) return;
+    if (nbest) {
+      auto s = sp.NBestEncodeBatch(batch, f.nbest_size, want_ids ? &nbest_ids : nullptr,
+                                   want_ids ? nullptr : &nbest_pieces, nullptr);
+      if (!s.ok()) Die(s.message);
+      for (size_t i = 0; i < batch.size(); ++i) {
+        const size_t paths = want_ids ? nbest_ids[i].size() : nbest_pieces[i].size();
+        for (size_t p = 0; p < paths; ++p) {
+          buf.clear();
+          if (want_ids) {
+            for (size_t k = 0; k < nbest_ids[i][p].size(); ++k) {
+              if (k) buf += ' ';
+              buf += std::to_string(nbest_ids[i][p][k]);
+            }
+          } else {
+            for (size_t k = 0; k < nbest_pieces[i][p].size(); ++k) {
+              if (k) buf += ' ';
+              buf += nbest_pieces[i][p][k];
+            }
+          }
+          buf += '\n';
+          out->write(buf.data(), buf.size());
+        }
+      }
+      batch.clear();
+      return;
+    }
     auto s = sample ? sp.SampleEncodeBatch(batch, f.nbest_size, f.alpha, want_ids ? &ids : nullptr,
                                            want_ids ? nullptr : &pieces)
                     : sp.EncodeBatch(batch, want_ids ? &ids : nullptr, want_ids ? nullptr : &pieces);

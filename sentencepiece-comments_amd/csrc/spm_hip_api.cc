@@ -21,6 +21,7 @@
 #include "bpe_tables.h"
 #include "device_model.h"
 #include "epilogue.h"
+#include "host_nbest.h"
 #include "kernels.h"
 #include "normalize_device.h"
 #include "normalizer.h"
@@ -266,6 +267,7 @@ int LoadUnigram(spm_hip_model *m) {
   m->ring_width = max_bytes < 16 ? 16 : max_bytes < 32 ? 32 : max_bytes < 64 ? 64 : 0;
   std::vector<float> scores(m->proto.pieces.size());
   for (size_t i = 0; i < scores.size(); ++i) scores[i] = m->proto.pieces[i].score;
+  m->host_scores = scores;
   bool nan_score = false;
   for (size_t u = 0; u < m->trie.units.size(); ++u) {
     if (!spm_amd::DoubleArray::Leaf(m->trie.units[u])) continue;
@@ -896,7 +898,9 @@ void EncodeWorkspace::Release() {
   svc_prof = nullptr;
   for (DevBuf *b : {&w_ctl, &w_slot_ids, &w_slot_len, &w_tprefix, &w_slot2_ids, &w_slot2_len, &w_ntok, &w_cnt, &w_bp, &w_flagged, &w_ovf, &w_scan,
                     &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_tids, &w_tlen, &w_ttok,
-                    &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask})
+                    &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask,
+                    &w_nb_ctl, &w_nb_npaths, &w_nb_stage, &w_nb_ntok, &w_nb_score, &w_nb_ids, &w_nb_len, &w_nb_hids,
+                    &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore})
     b->Release();
   if (pinned) (void)hipHostFree(pinned);
   pinned = nullptr;
@@ -2292,6 +2296,235 @@ int FetchHostBatch(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n, i
   return SPM_OK;
 }
 
+
+// ---- NBestEncode --------------------------------------------------------
+constexpr uint32_t kNBestSmallNb = 256;       // first tier: sentences up to this many bytes
+constexpr uint32_t kNBestLanes = 131072;      // first tier lanes, halved while the pool exceeds kNBestPool
+constexpr uint64_t kNBestPool = 4ull << 30;
+constexpr uint32_t kNBestLanes2 = 4096;       // second tier: at most this many lanes
+constexpr uint64_t kNBestMaxSlab = 4ull << 30;  // a longer sentence's lattice goes to the host
+constexpr uint64_t kNBestStageFull = 32ull << 20;  // token staging up to this many entries is sized by its bound
+
+spm_amd::HostNBestTables HostTables(const spm_hip_model *m, const std::vector<float> &scores) {
+  return spm_amd::HostNBestTables{m->trie.units.data(), static_cast<uint32_t>(m->trie.units.size()),
+                                  m->trie.values.data(), scores.data(), m->up};
+}
+
+int NBestArgsCheck(const spm_hip_model *m) {
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  if (m->model_type != spm_amd::kUnigram)
+    return Fail(SPM_UNIMPLEMENTED, "NBestEncode is implemented for unigram models only");
+  return SPM_OK;
+}
+
+// The search of one n-best call on a leased workspace: the two device tiers
+// and the host tier, then the two offset scans.  Leaves npaths / stage /
+// per-path counts and scores / token staging in the workspace, path offsets
+// in w_nb_poff and token offsets in w_nb_toff, and returns the totals.
+// h_bytes: the batch's bytes on the host when the caller has them (else the
+// host tier copies its sentences from the device).
+int NBestSearch(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *d_bytes, const uint64_t *d_off,
+                const uint8_t *h_bytes, uint64_t n, int N, bool with_len, uint64_t *total_paths,
+                uint64_t *total_tokens, hipStream_t st) {
+  *total_paths = *total_tokens = 0;
+  std::vector<uint64_t> off(n + 1);
+  SPM_HIP_TRY(hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  uint32_t max_nb = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (off[i + 1] < off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
+    if (off[i + 1] - off[i] > 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "sentence too long");
+    max_nb = std::max<uint32_t>(max_nb, static_cast<uint32_t>(off[i + 1] - off[i]));
+  }
+  const uint64_t total = off[n] - off[0];
+  if (n * static_cast<uint64_t>(N) >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many paths in one batch");
+  const int K = m->up.trie_results_size;
+  // Plan.  First tier: every sentence of <= nb1 bytes, hyps1 hypotheses each.
+  const uint32_t nb1 = std::max<uint32_t>(std::min(max_nb, kNBestSmallNb), 1);
+  const uint32_t knob1 = m->nbest_hyps1.load(), knob2 = m->nbest_hyps2.load();
+  uint32_t hyps1 = 2, hyps2 = 2;
+  if (N > 1) {
+    hyps1 = knob1 ? std::max(knob1, 2u) : 40u * N + 4u * nb1 + 64u;
+    hyps2 = knob2 ? std::max(knob2, 2u) : 16u * hyps1;
+  }
+  const uint64_t slab1 = spm_amd::UnigramNBestSlabBytes(nb1, K, hyps1);
+  uint32_t lanes1 = static_cast<uint32_t>(std::min<uint64_t>((n + 63) / 64 * 64, kNBestLanes));
+  while (lanes1 > 64 && lanes1 * slab1 > kNBestPool) lanes1 /= 2;
+  // Second tier: the longest sentence when its slab can be had, with the
+  // pool split among as many lanes as fit.
+  uint32_t nb2 = std::max<uint32_t>(max_nb, 1);
+  uint64_t slab2 = spm_amd::UnigramNBestSlabBytes(nb2, K, hyps2);
+  if (slab2 > kNBestMaxSlab) {
+    nb2 = nb1;
+    slab2 = spm_amd::UnigramNBestSlabBytes(nb2, K, hyps2);
+  }
+  if (slab2 > kNBestMaxSlab) return Fail(SPM_RESOURCE_EXHAUSTED, "n-best hypothesis arena too large");
+  const uint64_t pool = std::max<uint64_t>(lanes1 * slab1, slab2);
+  const uint32_t lanes2 = static_cast<uint32_t>(std::min<uint64_t>(pool / slab2, kNBestLanes2));
+  SPM_HIP_TRY(ws->w_scratch.Reserve(pool));
+  SPM_HIP_TRY(ws->w_ovf.Reserve(n * 4));
+  SPM_HIP_TRY(ws->w_nb_ovf2.Reserve(n * 4));
+  SPM_HIP_TRY(ws->w_nb_ctl.Reserve(16));
+  SPM_HIP_TRY(ws->w_nb_npaths.Reserve(n * 4));
+  SPM_HIP_TRY(ws->w_nb_stage.Reserve(n * 8));
+  SPM_HIP_TRY(ws->w_nb_ntok.Reserve(n * N * 4));
+  SPM_HIP_TRY(ws->w_nb_score.Reserve(n * N * 4));
+  SPM_HIP_TRY(ws->w_nb_poff.Reserve((n + 1) * 8));
+  SPM_HIP_TRY(hipMemsetAsync(ws->w_nb_npaths.ptr, 0, n * 4, st));
+  // Token staging: at most one token per byte per path; large batches start
+  // with a third of that bound and run again when the cursor passes it.
+  const uint64_t full = std::max<uint64_t>(total * N, 1);
+  uint64_t stage_cap = full <= kNBestStageFull ? full : std::max<uint64_t>(kNBestStageFull, full / 3);
+  uint32_t *ctl = ws->w_nb_ctl.as<uint32_t>();
+  uint32_t second = 0, host = 0;
+  const bool timing = TimedSlot(m, ws) >= 0;
+  for (int attempt = 0;; ++attempt) {
+    SPM_HIP_TRY(ws->w_nb_ids.Reserve(stage_cap * 4));
+    if (with_len) SPM_HIP_TRY(ws->w_nb_len.Reserve(stage_cap * 4));
+    SPM_HIP_TRY(hipMemsetAsync(ctl, 0, 16, st));
+    spm_amd::NBestLaunch a{d_bytes, d_off, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                           m->d_scores.as<float>(), static_cast<uint32_t>(m->trie.units.size()), m->up, N,
+                           nullptr, nullptr, n, ws->w_scratch.as<uint8_t>(), slab1, nb1, hyps1, lanes1,
+                           ws->w_ovf.as<uint32_t>(), ctl, ws->w_nb_npaths.as<uint32_t>(),
+                           ws->w_nb_stage.as<uint64_t>(), ws->w_nb_ntok.as<uint32_t>(), ws->w_nb_score.as<float>(),
+                           ws->w_nb_ids.as<int32_t>(), with_len ? ws->w_nb_len.as<uint32_t>() : nullptr, stage_cap,
+                           reinterpret_cast<unsigned long long *>(ctl + 2)};
+    if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
+    SPM_HIP_TRY(spm_amd::LaunchUnigramNBest(a, st));
+    // The overflow list with the pool split among fewer lanes (a device no-op
+    // when the list is empty).
+    a.list = ws->w_ovf.as<uint32_t>();
+    a.count = ctl;
+    a.list_n = 0;
+    a.slab_bytes = slab2;
+    a.max_nb = nb2;
+    a.max_hyps = hyps2;
+    a.lanes = lanes2;
+    a.ovf_list = ws->w_nb_ovf2.as<uint32_t>();
+    a.ovf_count = ctl + 1;
+    SPM_HIP_TRY(spm_amd::LaunchUnigramNBest(a, st));
+    if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
+    SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, ctl, 16, hipMemcpyDeviceToHost, st));
+    SPM_HIP_TRY(hipStreamSynchronize(st));
+    second = ws->pinned[0];
+    host = ws->pinned[1];
+    uint64_t cursor = 0;
+    std::memcpy(&cursor, ws->pinned + 2, 8);
+    if (cursor <= stage_cap) break;
+    if (attempt == 1) return Fail(SPM_INTERNAL, "n-best token staging overflow");
+    stage_cap = cursor;
+  }
+  if (second > n || host > second) return Fail(SPM_INTERNAL, "n-best overflow lists are inconsistent");
+  // Host tier: the same search over the host tables, its tokens in a staging
+  // buffer of their own (kNBestHostStage in stage[i]).  Sized for the few
+  // sentences expected there: one thread, four small uploads per sentence and,
+  // for a device-pointer call, one download of its bytes.
+  if (host) {
+    std::vector<uint32_t> list(host);
+    SPM_HIP_TRY(hipMemcpyAsync(list.data(), ws->w_nb_ovf2.ptr, host * 4ull, hipMemcpyDeviceToHost, st));
+    SPM_HIP_TRY(hipStreamSynchronize(st));
+    const spm_amd::HostNBestTables t = HostTables(m, m->host_scores);
+    std::vector<int32_t> hids;
+    std::vector<uint32_t> hlen;
+    std::vector<std::vector<uint32_t>> rows_ntok(host);
+    std::vector<std::vector<float>> rows_score(host);
+    std::vector<uint32_t> npaths(host);
+    std::vector<uint64_t> stage(host);
+    std::vector<uint8_t> sent;
+    std::vector<spm_amd::HostNBestPath> paths;
+    for (uint32_t j = 0; j < host; ++j) {
+      const uint32_t i = list[j];
+      if (i >= n) return Fail(SPM_INTERNAL, "n-best overflow list is out of range");
+      const uint32_t nb = static_cast<uint32_t>(off[i + 1] - off[i]);
+      const uint8_t *s = h_bytes ? h_bytes + off[i] : nullptr;
+      if (!s) {
+        sent.resize(nb);
+        SPM_HIP_TRY(hipMemcpyAsync(sent.data(), d_bytes + off[i], nb, hipMemcpyDeviceToHost, st));
+        SPM_HIP_TRY(hipStreamSynchronize(st));
+        s = sent.data();
+      }
+      spm_amd::HostNBest(t, s, nb, N, spm_amd::kNBestMaxAgenda, &paths, nullptr);
+      npaths[j] = static_cast<uint32_t>(paths.size());
+      stage[j] = spm_amd::kNBestHostStage | hids.size();
+      for (const auto &p : paths) {
+        rows_ntok[j].push_back(static_cast<uint32_t>(p.ids.size()));
+        rows_score[j].push_back(p.score);
+        hids.insert(hids.end(), p.ids.begin(), p.ids.end());
+        hlen.insert(hlen.end(), p.lens.begin(), p.lens.end());
+      }
+    }
+    SPM_HIP_TRY(ws->w_nb_hids.Reserve(std::max<size_t>(hids.size(), 1) * 4));
+    if (with_len) SPM_HIP_TRY(ws->w_nb_hlen.Reserve(std::max<size_t>(hids.size(), 1) * 4));
+    if (!hids.empty()) {
+      SPM_HIP_TRY(hipMemcpyAsync(ws->w_nb_hids.ptr, hids.data(), hids.size() * 4, hipMemcpyHostToDevice, st));
+      if (with_len)
+        SPM_HIP_TRY(hipMemcpyAsync(ws->w_nb_hlen.ptr, hlen.data(), hlen.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    for (uint32_t j = 0; j < host; ++j) {
+      const uint64_t i = list[j];
+      SPM_HIP_TRY(hipMemcpyAsync(ws->w_nb_npaths.as<uint32_t>() + i, &npaths[j], 4, hipMemcpyHostToDevice, st));
+      SPM_HIP_TRY(hipMemcpyAsync(ws->w_nb_stage.as<uint64_t>() + i, &stage[j], 8, hipMemcpyHostToDevice, st));
+      SPM_HIP_TRY(hipMemcpyAsync(ws->w_nb_ntok.as<uint32_t>() + i * N, rows_ntok[j].data(), npaths[j] * 4ull,
+                                 hipMemcpyHostToDevice, st));
+      SPM_HIP_TRY(hipMemcpyAsync(ws->w_nb_score.as<float>() + i * N, rows_score[j].data(), npaths[j] * 4ull,
+                                 hipMemcpyHostToDevice, st));
+    }
+    SPM_HIP_TRY(hipStreamSynchronize(st));  // the copies read these vectors
+  }
+  // path_off = scan of npaths; tok_off = scan of the paths' token counts.
+  size_t tmp = 0;
+  SPM_HIP_TRY(spm_amd::LaunchNBestPathOffsets(ws->w_nb_npaths.as<uint32_t>(), n, ws->w_nb_poff.as<uint64_t>(), nullptr,
+                                              &tmp, st));
+  SPM_HIP_TRY(ws->w_scan.Reserve(tmp + 16));
+  SPM_HIP_TRY(spm_amd::LaunchNBestPathOffsets(ws->w_nb_npaths.as<uint32_t>(), n, ws->w_nb_poff.as<uint64_t>(),
+                                              ws->w_scan.ptr, &tmp, st));
+  uint64_t P = 0, T = 0;
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 4, ws->w_nb_poff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(&P, ws->pinned + 4, 8);
+  if (P > n * static_cast<uint64_t>(N)) return Fail(SPM_INTERNAL, "n-best path count out of range");
+  SPM_HIP_TRY(ws->w_nb_ptok.Reserve(std::max<uint64_t>(P, 1) * 4));
+  SPM_HIP_TRY(ws->w_nb_toff.Reserve((P + 1) * 8));
+  SPM_HIP_TRY(spm_amd::LaunchNBestTokOffsets(n, N, ws->w_nb_npaths.as<uint32_t>(), ws->w_nb_poff.as<uint64_t>(),
+                                             ws->w_nb_ntok.as<uint32_t>(), P, ws->w_nb_ptok.as<uint32_t>(),
+                                             ws->w_nb_toff.as<uint64_t>(), nullptr, &tmp, st));
+  SPM_HIP_TRY(ws->w_scan.Reserve(tmp + 16));
+  SPM_HIP_TRY(spm_amd::LaunchNBestTokOffsets(n, N, ws->w_nb_npaths.as<uint32_t>(), ws->w_nb_poff.as<uint64_t>(),
+                                             ws->w_nb_ntok.as<uint32_t>(), P, ws->w_nb_ptok.as<uint32_t>(),
+                                             ws->w_nb_toff.as<uint64_t>(), ws->w_scan.ptr, &tmp, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 6, ws->w_nb_toff.as<uint64_t>() + P, 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(&T, ws->pinned + 6, 8);
+  *total_paths = P;
+  *total_tokens = T;
+  ws->stats = spm_hip_encode_stats{};
+  ws->stats.sentences = n;
+  ws->stats.tokens = T;
+  ws->stats.general_path = n;
+  if (timing) {
+    SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
+    ws->tcount = 0;
+  }
+  spm_amd::PublishStats(m, ws->stats);
+  {
+    std::lock_guard<std::mutex> lk(m->pool_mu);
+    m->nbest_second = second;
+    m->nbest_host = host;
+  }
+  return SPM_OK;
+}
+
+// The searched call's blocks to their final places (device pointers).
+int NBestGatherTo(spm_amd::EncodeWorkspace *ws, uint64_t n, int N, int32_t *d_ids, uint32_t *d_len, float *d_scores,
+                  hipStream_t st) {
+  const spm_amd::NBestGather g{n, static_cast<uint32_t>(N), ws->w_nb_poff.as<uint64_t>(),
+                               ws->w_nb_toff.as<uint64_t>(), ws->w_nb_stage.as<uint64_t>(),
+                               ws->w_nb_score.as<float>(), ws->w_nb_ids.as<int32_t>(), ws->w_nb_len.as<uint32_t>(),
+                               ws->w_nb_hids.as<int32_t>(), ws->w_nb_hlen.as<uint32_t>(), d_ids, d_len, d_scores};
+  SPM_HIP_TRY(spm_amd::LaunchNBestGather(g, st));
+  return SPM_OK;
+}
+
 }  // namespace
 
 int spm_hip_encode_raw_small_host(spm_hip_model *m, const uint8_t *raw, const uint64_t *raw_off, uint64_t n,
@@ -2406,6 +2639,96 @@ int spm_hip_sample_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, con
                       st);
   if (rc != SPM_OK) return rc;
   return FetchHostBatch(m, ws.get(), n, ids, len, tok, st);
+}
+
+int spm_hip_nbest_encode_batch(spm_hip_model *m, const uint8_t *d_bytes, const uint64_t *d_off, uint64_t n,
+                               int32_t nbest_size, int32_t *d_ids, uint32_t *d_len, uint64_t token_capacity,
+                               uint64_t *d_tok, float *d_scores, uint64_t path_capacity, uint64_t *d_path_off,
+                               uint64_t *total_paths, uint64_t *total_tokens, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_nbest_encode_batch");
+  if (!m || !d_off || !d_tok || !d_path_off) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  int rc = NBestArgsCheck(m);
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  const int N = spm_amd::NBestClamp(nbest_size);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForStream(m, st));
+  uint64_t P = 0, T = 0;
+  rc = NBestSearch(m, ws.get(), d_bytes, d_off, nullptr, n, N, d_len != nullptr, &P, &T, st);
+  if (rc != SPM_OK) return rc;
+  if (total_paths) *total_paths = P;
+  if (total_tokens) *total_tokens = T;
+  if (P > path_capacity || T > token_capacity)
+    return Fail(SPM_RESOURCE_EXHAUSTED, "n-best output exceeds the caller's capacities");
+  if ((T && !d_ids) || (P && !d_scores)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  SPM_HIP_TRY(hipMemcpyAsync(d_path_off, ws->w_nb_poff.ptr, (n + 1) * 8, hipMemcpyDeviceToDevice, st));
+  SPM_HIP_TRY(hipMemcpyAsync(d_tok, ws->w_nb_toff.ptr, (P + 1) * 8, hipMemcpyDeviceToDevice, st));
+  rc = NBestGatherTo(ws.get(), n, N, d_ids, d_len, d_scores, st);
+  if (rc != SPM_OK) return rc;
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  return SPM_OK;
+}
+
+int spm_hip_nbest_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                                    int32_t nbest_size, int32_t *ids, uint32_t *len, uint64_t token_capacity,
+                                    uint64_t *tok, float *scores, uint64_t path_capacity, uint64_t *path_off,
+                                    uint64_t *total_paths, uint64_t *total_tokens) {
+  spm_amd::TraceRange trace_range_("spm_hip_nbest_encode_batch_host");
+  if (!m || !off || !tok || !path_off) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  int rc = NBestArgsCheck(m);
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  if (off[0] != 0) return Fail(SPM_INVALID_ARGUMENT, "offsets must start at 0");
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
+  const uint64_t total = off[n];
+  if (total && !bytes) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  const int N = spm_amd::NBestClamp(nbest_size);
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForHost(m));
+  hipStream_t st = ws.stream();
+  SPM_HIP_TRY(ws->h_in.Reserve(std::max<uint64_t>(total, 1)));
+  SPM_HIP_TRY(ws->h_off.Reserve((n + 1) * 8));
+  if (total) SPM_HIP_TRY(hipMemcpyAsync(ws->h_in.ptr, bytes, total, hipMemcpyHostToDevice, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->h_off.ptr, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  uint64_t P = 0, T = 0;
+  rc = NBestSearch(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), bytes, n, N, len != nullptr, &P, &T,
+                   st);
+  if (rc != SPM_OK) return rc;
+  if (total_paths) *total_paths = P;
+  if (total_tokens) *total_tokens = T;
+  if (P > path_capacity || T > token_capacity)
+    return Fail(SPM_RESOURCE_EXHAUSTED, "n-best output exceeds the caller's capacities");
+  if ((T && !ids) || (P && !scores)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  SPM_HIP_TRY(ws->h_ids.Reserve(std::max<uint64_t>(T, 1) * 4));
+  if (len) SPM_HIP_TRY(ws->h_len.Reserve(std::max<uint64_t>(T, 1) * 4));
+  SPM_HIP_TRY(ws->w_nb_oscore.Reserve(std::max<uint64_t>(P, 1) * 4));
+  rc = NBestGatherTo(ws.get(), n, N, ws->h_ids.as<int32_t>(), len ? ws->h_len.as<uint32_t>() : nullptr,
+                     ws->w_nb_oscore.as<float>(), st);
+  if (rc != SPM_OK) return rc;
+  SPM_HIP_TRY(hipMemcpyAsync(path_off, ws->w_nb_poff.ptr, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipMemcpyAsync(tok, ws->w_nb_toff.ptr, (P + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (T) SPM_HIP_TRY(hipMemcpyAsync(ids, ws->h_ids.ptr, T * 4, hipMemcpyDeviceToHost, st));
+  if (T && len) SPM_HIP_TRY(hipMemcpyAsync(len, ws->h_len.ptr, T * 4, hipMemcpyDeviceToHost, st));
+  if (P) SPM_HIP_TRY(hipMemcpyAsync(scores, ws->w_nb_oscore.ptr, P * 4, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  return SPM_OK;
+}
+
+int spm_hip_model_set_nbest_max_hyps(spm_hip_model *m, uint32_t first, uint32_t second) {
+  if (!m) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  m->nbest_hyps1 = first;
+  m->nbest_hyps2 = second;
+  return SPM_OK;
+}
+
+int spm_hip_nbest_last_stats(const spm_hip_model *m, uint64_t *second_pass, uint64_t *host_path) {
+  if (!m) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  std::lock_guard<std::mutex> lk(const_cast<spm_hip_model *>(m)->pool_mu);
+  if (second_pass) *second_pass = m->nbest_second;
+  if (host_path) *host_path = m->nbest_host;
+  return SPM_OK;
 }
 
 int spm_hip_sample_uniform(uint64_t seed, uint64_t index, uint64_t draw, double *u) {

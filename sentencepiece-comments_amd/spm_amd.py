@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPM_AMD_LIB") or os.path.join(HERE, "lib", "libspm_hip.so")
 
 SPM_OK = 0
+SPM_RESOURCE_EXHAUSTED = 8
 SPM_UNIGRAM, SPM_BPE = 1, 2
 SPM_ESTEP_FAST, SPM_ESTEP_PARITY = 0, 1
 SPM_ESTEP_DEFER_FOLD = 0x100  # include/spm_hip.h
@@ -42,6 +43,8 @@ EXPORTED = [
     "spm_hip_estep_kernel_times", "spm_hip_device_bytes", "spm_hip_device_peak_reset",
     "spm_hip_encode_raw_small_host", "spm_hip_model_piece_lookup",
     "spm_hip_sample_encode_batch", "spm_hip_sample_encode_batch_host", "spm_hip_sample_uniform",
+    "spm_hip_nbest_encode_batch", "spm_hip_nbest_encode_batch_host", "spm_hip_model_set_nbest_max_hyps",
+    "spm_hip_nbest_last_stats",
 ]
 
 ABI_VERSION = 3  # SPM_HIP_ABI_VERSION of include/spm_hip.h (struct layouts below)
@@ -198,6 +201,13 @@ def lib():
         L.spm_hip_sample_encode_batch.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P, P]
         L.spm_hip_sample_encode_batch_host.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P]
         L.spm_hip_sample_uniform.argtypes = [U64, U64, U64, ctypes.POINTER(ctypes.c_double)]
+        I32 = ctypes.c_int32
+        L.spm_hip_nbest_encode_batch.argtypes = [P, P, P, U64, I32, P, P, U64, P, P, U64, P, ctypes.POINTER(U64),
+                                                 ctypes.POINTER(U64), P]
+        L.spm_hip_nbest_encode_batch_host.argtypes = [P, P, P, U64, I32, P, P, U64, P, P, U64, P,
+                                                      ctypes.POINTER(U64), ctypes.POINTER(U64)]
+        L.spm_hip_model_set_nbest_max_hyps.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32]
+        L.spm_hip_nbest_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_device_peak_reset.restype = None
         _lib = L
     return _lib
@@ -456,6 +466,63 @@ class DeviceModel:
                                                    ctypes.c_void_p(d_len) if d_len else None,
                                                    ctypes.c_void_p(d_tok),
                                                    ctypes.c_void_p(stream) if stream else None))
+
+    def nbest_encode_csr_host(self, buf, off, nbest_size, with_lens=False, capacities=None):
+        """NBestEncode of host CSR sentences: the nbest_size best segmentations
+        of each, best first.  Returns (ids int32, tok_off uint64[P + 1],
+        path_off uint64[n + 1], scores float32[P][, piece_len uint32]): sentence
+        i owns paths path_off[i]..path_off[i + 1], path p owns tokens
+        tok_off[p]..tok_off[p + 1].  Capacities start from a guess (16 tokens
+        per path) and the call is repeated once with the totals it returned;
+        capacities=(tokens, paths) sets the first try."""
+        n = len(off) - 1
+        N = max(1, min(int(nbest_size), 1024))
+        tcap, pcap = capacities if capacities else (min(N * int(off[-1]), 16 * N * n + 1024), n * N)
+        tp, tt = ctypes.c_uint64(), ctypes.c_uint64()
+        for attempt in range(2):
+            ids = np.zeros(max(tcap, 1), dtype=np.int32)
+            lens = np.zeros(max(tcap, 1), dtype=np.uint32) if with_lens else None
+            to = np.zeros(pcap + 1, dtype=np.uint64)
+            sc = np.zeros(max(pcap, 1), dtype=np.float32)
+            po = np.zeros(n + 1, dtype=np.uint64)
+            rc = self._L.spm_hip_nbest_encode_batch_host(self.h, _p(buf), _p(off), n, int(nbest_size), _p(ids),
+                                                         _p(lens) if with_lens else None, tcap, _p(to), _p(sc), pcap,
+                                                         _p(po), ctypes.byref(tp), ctypes.byref(tt))
+            if rc != SPM_RESOURCE_EXHAUSTED or attempt == 1:
+                break
+            tcap, pcap = tt.value, tp.value
+        _check(rc)
+        P, T = tp.value, tt.value
+        out = (ids[:T], to[:P + 1], po, sc[:P])
+        return out + (lens[:T],) if with_lens else out
+
+    def nbest_encode_device(self, d_bytes, d_off, n, nbest_size, d_ids, token_capacity, d_tok, d_scores,
+                            path_capacity, d_path_off, d_len=None, stream=None):
+        """spm_hip_nbest_encode_batch on device pointers (ints); blocking.
+        Returns (total_paths, total_tokens); raises SpmError (code 8, with
+        .totals set) when a capacity is too small."""
+        tp, tt = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self._L.spm_hip_nbest_encode_batch(self.h, ctypes.c_void_p(d_bytes), ctypes.c_void_p(d_off), n,
+                                                int(nbest_size), ctypes.c_void_p(d_ids),
+                                                ctypes.c_void_p(d_len) if d_len else None, token_capacity,
+                                                ctypes.c_void_p(d_tok), ctypes.c_void_p(d_scores), path_capacity,
+                                                ctypes.c_void_p(d_path_off), ctypes.byref(tp), ctypes.byref(tt),
+                                                ctypes.c_void_p(stream) if stream else None)
+        if rc != SPM_OK:
+            e = SpmError(rc, self._L.spm_hip_last_error().decode(errors="replace"))
+            e.totals = (tp.value, tt.value)
+            raise e
+        return tp.value, tt.value
+
+    def set_nbest_max_hyps(self, first, second):
+        """Testing knob: hypothesis arenas of the two device tiers (0 = automatic)."""
+        _check(self._L.spm_hip_model_set_nbest_max_hyps(self.h, first, second))
+
+    def nbest_stats(self):
+        """(second_pass, host_path) of the last n-best call."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._L.spm_hip_nbest_last_stats(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def encode_normalized(self, sentences):
         buf, off = to_csr(sentences)
