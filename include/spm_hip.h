@@ -73,7 +73,14 @@ typedef struct spm_hip_model_info {
                                piece in bytes), 0 = general kernel only */
   int32_t fast_variant;     /* unigram encode kernel: 1 byte-position kernel
                                (W = 16), 2 char-position kernel, 3 wide-char
-                               kernel (ring of 16 chars), 0 general only */
+                               kernel (ring of 16 chars), 0 general only.
+                               BPE: the kernel first in line: 1 lane kernel
+                               with rank ids, merged id = base - rank; 2 lane
+                               kernel with rank ids, merged id from the rank
+                               table; 3 lane kernel with 32-bit symbol words
+                               (tied merge scores); 4 half kernel (>= 32768
+                               pieces); 0 general kernel only (user-defined
+                               symbols).  Also set on a host-only handle. */
 } spm_hip_model_info;
 
 /* Counters of the last encode call (host-visible after it returns). */

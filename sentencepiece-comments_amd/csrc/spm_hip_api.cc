@@ -1138,7 +1138,13 @@ int spm_hip_model_get_info(const spm_hip_model *m, spm_hip_model_info *info) {
   info->min_score = m->min_score;
   info->max_score = m->max_score;
   info->ring_width = m->model_type == spm_amd::kUnigram ? m->ring_width : 0;
-  info->fast_variant = m->model_type == spm_amd::kUnigram ? static_cast<int32_t>(m->kernel) : 0;
+  if (m->model_type == spm_amd::kUnigram) {
+    info->fast_variant = static_cast<int32_t>(m->kernel);
+  } else {
+    // The BPE encode tier, from what LoadBpe decided (EncodeBpe's branches).
+    const auto &b = m->bpe;
+    info->fast_variant = b.has_user_defined ? 0 : !b.lane_ok ? 4 : !b.rank_ids ? 3 : b.rank_base >= 0 ? 1 : 2;
+  }
   return SPM_OK;
 }
 

@@ -261,6 +261,13 @@ class DeviceModel:
         self.close()
 
     def info(self):
+        """spm_hip_model_info (works on a host-only handle too).  fast_variant
+        names the encode kernel first in line.  Unigram: 1 byte kernel, 2 char
+        kernel, 3 wide-char kernel, 0 general only (ring_width: its ring).
+        BPE (ring_width 0): 1 lane kernel, rank ids, merged id = base - rank;
+        2 lane kernel, rank ids, merged id from the rank table; 3 lane kernel
+        with 32-bit symbol words (tied merge scores); 4 half kernel (>= 32768
+        pieces); 0 general kernel only (user-defined symbols)."""
         inf = ModelInfo()
         _check(self._L.spm_hip_model_get_info(self.h, ctypes.byref(inf)))
         return inf
