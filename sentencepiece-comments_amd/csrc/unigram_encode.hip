@@ -26,7 +26,9 @@
 // Two forward passes:
 //   kByte (W = 16, models whose pieces are whole chars of < 16 bytes): every
 //     byte position is visited, char starts found by the lead-byte chain;
-//     positions walked in pairs (two independent trie-load chains per lane),
+//     positions walked in pairs (two independent trie-load chains per lane
+//     up to depth 5, one chain per lane past it, a second pass for the lanes
+//     with two deep chains),
 //     inserts lagged one walk step behind their score loads (software
 //     pipeline), back-pointers packed as 8-bit distances, 2 near-tie entries,
 //     7 waves/SIMD.  (Round-2 A/B of the alternatives — LDS trie top, jump
@@ -479,6 +481,39 @@ void unigram_fast_kernel(FastArgs a) {
       T[k] = lanes_of(gtm) ? bt : T[k];
       SetByteIf<k & 3, d>(Bw[k >> 2], gtm);
     };
+    // The merged deep phase's insert at walk step e of the pair at jb = k + 1
+    // - e (slot k, end position `end`): a lane carries one chain there, chain
+    // 1 (begin jb + 1, node length e - 2) in the lanes of sm and chain 0
+    // (begin jb, length e - 1) in the others; sc is the lane's own node score
+    // and T0 / tie_bound its own position's.  No UNK select: e - 2 > 4.
+    auto insert_m = [&](auto kc, auto ec, uint32_t end, Mask sm, float T0, float tie_bound, float sc) {
+      constexpr int k = decltype(kc)::value;
+      constexpr int e = decltype(ec)::value;
+      static_assert(e - 2 > 4 && e - 2 < W && k < kR, "a deep node of the pair");
+      const float bt = __fadd_rn(T0, sc);
+      float tk = T[k];
+      if constexpr (e >= W) __asm__ volatile("" : "+v"(tk));  // as insert_one's depth W - 1
+      const Mask gtm = __builtin_amdgcn_ballot_w64(bt > tk);  // false for NaN
+      const Mask nearm = gtm & __builtin_amdgcn_ballot_w64(NearTieAt(tk, bt, tie_bound));
+      if (nearm != 0 || amb_wave) {
+        const bool nr = lanes_of(nearm);
+        if (nr || (lanes_of(gtm) && ((ambm >> k) & 1)))
+          amb_update(std::integral_constant<int, k>{}, bt, nr, end, T[k], end - b_dist(std::integral_constant<int, k>{}));
+        amb_wave = __builtin_amdgcn_ballot_w64(ambm != 0) != 0;
+      }
+      T[k] = lanes_of(gtm) ? bt : T[k];
+      if constexpr (e - 1 < W) SetByteIf<k & 3, e - 1>(Bw[k >> 2], gtm & ~sm);
+      SetByteIf<k & 3, e - 2>(Bw[k >> 2], gtm & sm);
+    };
+    // Walk steps 1 .. kMergeDepth test and gather both chains of a pair; past
+    // them a lane carries one chain (see the merged deep phase below).  Chain
+    // 1's node of length 4, the last with an UNK select, is inserted in every
+    // lane at step 6, so the merged inserts start at step 7 at the earliest.
+    // (Depth 4 with step 6 kept two-chain measured the same as 5, depth 6
+    // 1.4 % slower: profiles/pr12_c2_merged_walk_ab.txt.)
+    constexpr int kMergeDepth = 5;
+    constexpr bool kMerge = !kE;  // the E-step mode keeps its two-chain deep steps
+    static_assert(kMergeDepth >= 5 && kMergeDepth + 2 < W, "merged inserts hold no node of length <= 4");
     uint32_t next_start = 0;
     for (uint32_t p0 = 0; p0 <= nb; p0 += kU) {
       StaticFor<0, kU / kNI>([&](auto pc) {
@@ -560,9 +595,41 @@ void unigram_fast_kernel(FastArgs a) {
         // its label is 0xFF (as every empty unit's), which no byte of an
         // unflagged sentence matches, so the lane stays out without a flag
         // of its own, and "alive" is one compare per step.
-        StaticFor<1, W + kNI>([&](auto dc) {
+        // Merged deep phase state (kMerge): the lanes that carry chain 1, the
+        // lanes whose two chains are both alive at kMergeDepth (chain 1 of
+        // those runs in a second pass, from its saved unit and score), the
+        // lane's own T0 / tie bound, its byte selector (v_perm: byte t of the
+        // window for chain 0, t + 1 for chain 1), the pending gather and the
+        // label it will be tested against.
+        Mask selm = 0, bothm = 0;
+        bool mgo = false;
+        uint32_t uB = 0, psel = 0, cm = 0;
+        float sB = 0.f, sD = 0.f, T0m = 0.f, Tbm = 0.f;
+        UvT muv;
+        auto mbyte = [&](auto tc) -> uint32_t {
+          constexpr int t = decltype(tc)::value;
+          uint32_t hi = 0u;
+          if constexpr ((t >> 2) + 1 < kWin) hi = rw[(t >> 2) + 1];
+          return __builtin_amdgcn_perm(hi, rw[t >> 2], psel + static_cast<uint32_t>(t & 3));
+        };
+        // Enters a pass of the merged phase: lanes of `sm` carry chain 1, the
+        // others chain 0; `alive` lanes continue from `unit` (alive at depth
+        // kMergeDepth), the others gather pair 0 from here on.
+        auto merged_enter = [&](Mask sm, Mask alive, uint32_t unit, float s_d) {
+          selm = sm;
+          const bool sl = lanes_of(sm);
+          T0m = sl ? T0q[1] : T0q[0];
+          Tbm = sl ? Tbq[1] : Tbq[0];
+          psel = sl ? 0x0C0C0C01u : 0x0C0C0C00u;
+          sD = s_d;
+          cm = mbyte(std::integral_constant<int, jb + kMergeDepth>{});
+          uint32_t o = lanes_of(alive) ? ((unit >> 9) ^ cm) << 3 : 0u;
+          __asm__ volatile("" : "+v"(o));
+          muv = __builtin_amdgcn_raw_buffer_load_b64(uvs_rsrc, o, 0, 0);
+        };
+        StaticFor<1, kMerge ? kMergeDepth + 2 : W + kNI>([&](auto dc) {
           constexpr int d = decltype(dc)::value;
-          if constexpr (d < W) {
+          if constexpr (d < W && (!kMerge || d <= kMergeDepth)) {
             StaticFor<0, kNI>([&](auto qc) { sok[decltype(qc)::value][d] = __builtin_nanf(""); });
             if (go) {
               Mask alm[kNI];
@@ -574,7 +641,18 @@ void unigram_fast_kernel(FastArgs a) {
                 if (alm[q] != 0) dm[q] = d;
               });
               go = (alm[0] | alm[1]) != 0;
-              if constexpr (d + 1 < W) {
+              if constexpr (kMerge && d == kMergeDepth) {
+                // One gather per lane from here on: chain 1 where it alone
+                // is alive, else chain 0.
+                if (go) {
+                  mgo = true;
+                  bothm = alm[0] & alm[1];
+                  uB = uv[1][0];
+                  sB = sok[1][d];
+                  const Mask sm = alm[1] & ~alm[0];
+                  merged_enter(sm, alm[0] | alm[1], lanes_of(sm) ? uv[1][0] : uv[0][0], sok[1][d]);
+                }
+              } else if constexpr (d + 1 < W) {
                 if (go) {
                   StaticFor<0, kNI>([&](auto qc) {
                     constexpr int q = decltype(qc)::value;
@@ -622,6 +700,68 @@ void unigram_fast_kernel(FastArgs a) {
             }
           });
         });
+        // ---- Merged deep phase.  Past depth kMergeDepth a lane rarely has
+        // both chains of its pair alive (a deep walk starts at a "▁"), so
+        // step e > kMergeDepth tests one label, issues one gather and runs
+        // one insert into slot jb + e - 1: chain 0's node of length e - 1 or
+        // chain 1's of length e - 2, whichever chain the lane carries.  The
+        // lanes with two deep chains carry chain 0 in pass A and chain 1 in
+        // pass B, the same unrolled body run once more.  Ring slots are only
+        // written here (a position's own slot is read at step q + 2), and a
+        // slot still gets one lane's chain 0 node before its chain 1 node:
+        // with one deep chain the other insert was a NaN no-op, with two,
+        // pass A is complete before pass B starts.  Every slot sees the same
+        // setters in the same order as in the two-chain walk.  (The two
+        // near-tie entries are shared by all slots: a lane with two deep
+        // chains whose entries fill up in pass A before a pass-B setter would
+        // have freed one is flagged where the two-chain order was not, and
+        // the general kernel then emits the same tokens.)
+        if constexpr (kMerge) {
+          if (mgo) {
+#pragma clang loop unroll(disable)
+            for (int pass = 0;; ++pass) {
+              float S[W];  // the carried chain's node score of depth e (NaN: no usable node)
+              S[kMergeDepth] = sD;
+              int mdm = kMergeDepth;
+              bool g = true;
+              StaticFor<kMergeDepth + 1, W + kNI>([&](auto ec) {
+                constexpr int e = decltype(ec)::value;
+                if constexpr (e < W) {
+                  S[e] = __builtin_nanf("");
+                  if (g) {
+                    const Mask al = __builtin_amdgcn_ballot_w64((muv[0] & 0xFFu) == cm);
+                    S[e] = lanes_of(al) ? __uint_as_float(muv[1]) : __builtin_nanf("");
+                    if (al != 0) mdm = e;
+                    g = al != 0;
+                    if constexpr (e + 1 < W) {
+                      if (g) {
+                        cm = mbyte(std::integral_constant<int, jb + e>{});
+                        uint32_t o = lanes_of(al) ? ((muv[0] >> 9) ^ cm) << 3 : 0u;
+                        __asm__ volatile("" : "+v"(S[e]), "+v"(o));
+                        muv = __builtin_amdgcn_raw_buffer_load_b64(uvs_rsrc, o, 0, 0);
+                      }
+                    }
+                  }
+                }
+                if constexpr (e >= kMergeDepth + 2) {
+                  if (e - 2 <= mdm) {
+                    float sc;
+                    if constexpr (e - 1 < W) sc = lanes_of(selm) ? S[e - 2] : S[e - 1];
+                    else sc = lanes_of(selm) ? S[e - 2] : __builtin_nanf("");
+                    // No lane has a usable node here (three merged inserts in ten on c2): one compare.
+                    if (__builtin_amdgcn_ballot_w64(sc == sc) != 0)
+                      insert_m(std::integral_constant<int, jb + e - 1>{}, ec, pp[0] + static_cast<uint32_t>(e - 1), selm,
+                               T0m, Tbm, sc);
+                  }
+                }
+              });
+              if (pass != 0 || bothm == 0) break;
+              // Pass B: chain 1 of the lanes with two deep chains, every
+              // other lane dead from the start.
+              merged_enter(~static_cast<Mask>(0), bothm, uB, lanes_of(bothm) ? sB : __builtin_nanf(""));
+            }
+          }
+        }
       });
       // Next group: shift the ring and the byte window by kU.
 #pragma unroll
