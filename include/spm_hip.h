@@ -19,6 +19,8 @@
  *   spm_hip_finalize_ids SentencePieceProcessor::PopulateSentencePieceText +
  *                        ApplyExtraOptions (src/sentencepiece_processor.cc:488-551,
  *                        :945-979), id part
+ *   spm_hip_decode_batch SentencePieceProcessor::Decode(ids) (src/sentencepiece_processor.cc:
+ *                        670-733) with the decode extra options (:945-979)
  *   spm_hip_estep        unigram::Trainer::RunEStep (src/unigram_model_trainer.cc:237-287)
  *   spm_hip_seed_mine    unigram::Trainer::MakeSeedSentencePieces
  *                        (src/unigram_model_trainer.cc:124-225) + esaxx
@@ -388,6 +390,61 @@ int spm_hip_finalize_ids_async(spm_hip_model *model, const char *extra_options, 
                                const uint64_t *d_tok_offsets, uint64_t n, int32_t *d_out_ids,
                                uint64_t out_capacity, uint64_t *d_out_offsets, uint32_t *d_status,
                                void *stream);
+
+/* Batched SentencePieceProcessor::Decode(ids) on the device
+ * (sentencepiece_processor.cc:670-733): ids -> text.  DEVICE pointers:
+ * d_ids / d_tok_offsets[n+1] as produced by spm_hip_encode_batch or
+ * spm_hip_finalize_ids (the offsets index d_ids and need not start at 0).
+ *
+ * Per sentence: the id list, then the option string of
+ * SetDecodeExtraOptions ("bos:eos:reverse" applied in the order given,
+ * ApplyExtraOptions :945-979, parsed as ParseExtraOptions :981-1023 with its
+ * messages; NULL or "" = none), then the surfaces left to right: a CONTROL
+ * id gives "", the UNKNOWN id gives TrainerSpec.unk_surface (" \xE2\x81\x87 "
+ * unless the model sets it), any other id gives its piece with every U+2581
+ * replaced by one space, after one leading U+2581 is dropped if the text built
+ * so far is empty (so [<s>, U+2581, U+2581, U+2581 ABC] decodes to "ABC").
+ *
+ * Output: d_out_bytes (capacity out_capacity bytes; tokens *
+ * spm_hip_model_decode_bound always suffices, tokens counting the bos/eos
+ * pieces) and d_out_offsets[n+1], sentence i = bytes [offsets[i],
+ * offsets[i+1]).  d_piece_begin (may be NULL): one uint32 per output token in
+ * final order (tok_offsets[n] - tok_offsets[0] + n * (number of bos and eos
+ * options) entries), the sentence-relative byte offset where the token's
+ * surface begins (SentencePieceText begin; end = the next token's begin, or
+ * the sentence's length).  *total (may be NULL) receives the byte count.
+ * d_out_bytes == NULL counts only: the offsets and *total, nothing else.
+ * If the text exceeds out_capacity, the offsets and *total are produced, no
+ * text byte and no begin is written and SPM_RESOURCE_EXHAUSTED is returned.
+ *
+ * The reference indexes pieces(id) unchecked; here an id outside [0,
+ * piece_size) gives SPM_OUT_OF_RANGE (the message names the first such
+ * sentence and id) and no output is written at all.  One small read-back. */
+int spm_hip_decode_batch(spm_hip_model *model, const char *extra_options, const int32_t *d_ids,
+                         const uint64_t *d_tok_offsets, uint64_t n, uint8_t *d_out_bytes,
+                         uint64_t out_capacity, uint64_t *d_out_offsets, uint32_t *d_piece_begin,
+                         uint64_t *total, void *stream);
+
+/* Pure stream version of spm_hip_decode_batch (status-word contract of
+ * spm_hip_encode_batch_async: nothing is read or written once *d_status is
+ * non-zero; OUT_OF_RANGE or RESOURCE_EXHAUSTED land there, first error wins;
+ * the byte count is in d_out_offsets[n]). */
+int spm_hip_decode_batch_async(spm_hip_model *model, const char *extra_options, const int32_t *d_ids,
+                               const uint64_t *d_tok_offsets, uint64_t n, uint8_t *d_out_bytes,
+                               uint64_t out_capacity, uint64_t *d_out_offsets, uint32_t *d_piece_begin,
+                               uint32_t *d_status, void *stream);
+
+/* Same contract with HOST buffers (offsets start at 0): uploads, decodes on
+ * the device and downloads.  On a host-only handle the same result comes from
+ * a plain loop on the calling thread, no GPU needed. */
+int spm_hip_decode_batch_host(spm_hip_model *model, const char *extra_options, const int32_t *ids,
+                              const uint64_t *tok_offsets, uint64_t n, uint8_t *out_bytes,
+                              uint64_t out_capacity, uint64_t *out_offsets, uint32_t *piece_begin,
+                              uint64_t *total);
+
+/* The longest surface of any id, in bytes: tokens * bound sizes a decode
+ * output without the count call.  Works on host-only handles. */
+int spm_hip_model_decode_bound(const spm_hip_model *model, uint32_t *max_surface_bytes);
 
 /* Debug/testing knob: 1 = route every sentence through the exact general
  * kernel (reference-structured lattice), 0 = fast path with automatic

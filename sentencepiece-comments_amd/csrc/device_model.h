@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/spm_hip.h"
+#include "decode.h"
 #include "device_types.h"
 #include "double_array.h"
 #include "kernels.h"
@@ -53,6 +54,9 @@ struct EncodeWorkspace {
       w_nb_ovf2, w_nb_poff, w_nb_ptok, w_nb_toff, w_nb_oscore;
   DevBuf w_nlen, w_nscan;    // device normalizer: lengths, scan temp
   DevBuf w_ecount, w_escan;  // id epilogue: counts, scan temp
+  // Decode: first non-empty position per sentence, block sums, control words;
+  // staging of the host entry (ids, token offsets, text, offsets, begins).
+  DevBuf w_dfirst, w_dsum, w_dctl, h_dids, h_dtok, h_dout, h_doff, h_dbegin;
   DevBuf w_tids, w_tlen, w_ttok;  // SentencePieceText path: raw ids, piece lengths, token offsets
   DevBuf h_in, h_off, h_ids, h_len, h_tok;  // staging for the host API
   // Host API small batches (EncodeHostSmall): one device block [control |
@@ -167,6 +171,9 @@ struct spm_hip_model {
   uint32_t ud_units_n = 0;
   spm_amd::DevBuf d_types;
   std::atomic<bool> types_ready{false};
+  // Decode table (decode.h), built at load; the device copy unless host_only.
+  spm_amd::DecodeTable decode;
+  spm_amd::DevBuf d_dec_meta, d_dec_off, d_dec_bytes;
   // Workspaces (under pool_mu): one per caller stream, a pool for the host API.
   std::mutex pool_mu;
   std::unordered_map<hipStream_t, std::unique_ptr<spm_amd::EncodeWorkspace>> by_stream;

@@ -6,6 +6,7 @@
 #include "scratch_cache.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iterator>
@@ -138,14 +139,11 @@ int SentencePieceProcessor::pad_id() const {
   return IsControl(id) ? id : -1;
 }
 
-// ParseExtraOptions (sentencepiece_processor.cc:981-1010).
-Status SentencePieceProcessor::SetEncodeExtraOptions(const std::string &opts) {
-  extra_.clear();
-  extra_str_.clear();
+// ParseExtraOptions (sentencepiece_processor.cc:981-1023).
+Status SentencePieceProcessor::ParseExtraOptions(const std::string &opts, std::vector<ExtraOption> *out) const {
+  out->clear();
   if (opts.empty()) return Status::Ok();
   if (!status_.ok()) return status_;
-  std::stringstream ss(opts);
-  std::string tok;
   std::vector<std::string> parts;
   size_t st = 0;
   while (true) {
@@ -159,18 +157,33 @@ Status SentencePieceProcessor::SetEncodeExtraOptions(const std::string &opts) {
     if (s == "bos") {
       if (IsUnknown(PieceToId(proto_.trainer_spec.bos_piece)))
         return Err(SPM_INTERNAL, "id for `" + proto_.trainer_spec.bos_piece + "` is not defined.");
-      extra_.push_back(BOS);
+      out->push_back(BOS);
     } else if (s == "eos") {
       if (IsUnknown(PieceToId(proto_.trainer_spec.eos_piece)))
         return Err(SPM_INTERNAL, "id for `" + proto_.trainer_spec.eos_piece + "` is not defined.");
-      extra_.push_back(EOS);
+      out->push_back(EOS);
     } else if (s == "reverse") {
-      extra_.push_back(REVERSE);
+      out->push_back(REVERSE);
     } else {
       return Err(SPM_INTERNAL, "option \"" + s + "\" is not available.");
     }
   }
+  return Status::Ok();
+}
+
+Status SentencePieceProcessor::SetEncodeExtraOptions(const std::string &opts) {
+  extra_str_.clear();
+  const Status st = ParseExtraOptions(opts, &extra_);
+  if (!st.ok()) return st;  // like the reference, the options parsed so far stay
   extra_str_ = opts;
+  return Status::Ok();
+}
+
+Status SentencePieceProcessor::SetDecodeExtraOptions(const std::string &opts) {
+  decode_extra_str_.clear();
+  const Status st = ParseExtraOptions(opts, &decode_extra_);
+  if (!st.ok()) return st;
+  decode_extra_str_ = opts;
   return Status::Ok();
 }
 
@@ -644,6 +657,206 @@ Status SentencePieceProcessor::Encode(const std::string &input,
   std::vector<std::vector<std::string>> out;
   Status st = EncodeBatch({input}, nullptr, &out);
   if (st.ok()) *pieces = std::move(out[0]);
+  return st;
+}
+
+// ---------------------------------------------------------------------------
+// Decode (sentencepiece_processor.cc:341-370, :670-733).
+
+namespace {
+
+const char kSpaceSymbol[] = "\xE2\x96\x81";  // U+2581
+
+SentencePieceProcessor::DecodePath DecodePathFromEnv() {
+  static const SentencePieceProcessor::DecodePath kPath = [] {
+    const char *e = std::getenv("SPM_HIP_DECODE_PATH");
+    const std::string v = e ? e : "";
+    if (v == "host") return SentencePieceProcessor::kDecodeHost;
+    if (v == "device") return SentencePieceProcessor::kDecodeDevice;
+    return SentencePieceProcessor::kDecodeAuto;
+  }();
+  return kPath;
+}
+
+}  // namespace
+
+// ApplyExtraOptions (:945-979) over (piece, id) rows, then the surface loop of
+// Decode (:678-713).
+void SentencePieceProcessor::DecodeLineHost(std::vector<std::pair<std::string, int>> *row, std::string *text,
+                                            std::vector<DecodedPiece> *spt) const {
+  const auto &ts = proto_.trainer_spec;
+  for (const ExtraOption o : decode_extra_) {
+    if (o == REVERSE) std::reverse(row->begin(), row->end());
+    else if (o == EOS) row->emplace_back(ts.eos_piece, PieceToId(ts.eos_piece));
+    else row->insert(row->begin(), std::make_pair(ts.bos_piece, PieceToId(ts.bos_piece)));
+  }
+  if (!text) return;  // options only
+  text->clear();
+  std::string surface;
+  for (const auto &pi : *row) {
+    const std::string &piece = pi.first;
+    const int id = pi.second;
+    surface.clear();
+    if (IsControl(id)) {
+    } else if (IsUnknown(id)) {
+      surface = IdToPiece(id) == piece ? ts.unk_surface : piece;
+    } else {
+      size_t k = text->empty() && piece.compare(0, 3, kSpaceSymbol) == 0 ? 3 : 0;
+      while (k < piece.size()) {
+        if (piece.compare(k, 3, kSpaceSymbol) == 0) {
+          surface.push_back(' ');
+          k += 3;
+        } else {
+          surface.push_back(piece[k++]);
+        }
+      }
+    }
+    if (spt) {
+      DecodedPiece d;
+      d.piece = piece;
+      d.id = id;
+      d.surface = surface;
+      d.begin = static_cast<uint32_t>(text->size());
+      d.end = static_cast<uint32_t>(text->size() + surface.size());
+      spt->push_back(std::move(d));
+    }
+    *text += surface;
+  }
+}
+
+Status SentencePieceProcessor::DecodeRows(std::vector<std::vector<std::pair<std::string, int>>> *rows,
+                                          const std::vector<char> &oov, std::vector<std::string> *texts,
+                                          std::vector<std::vector<DecodedPiece>> *spt) const {
+  const size_t n = rows->size();
+  const int v = GetPieceSize();
+  uint64_t tokens = 0;
+  for (size_t i = 0; i < n; ++i) {
+    for (const auto &pi : (*rows)[i])
+      if (pi.second < 0 || pi.second >= v)
+        return Err(SPM_OUT_OF_RANGE, "decode: sentence " + std::to_string(i) + " holds id " +
+                                         std::to_string(pi.second) + ", outside [0, " + std::to_string(v) + ")");
+    tokens += (*rows)[i].size();
+  }
+  texts->assign(n, std::string());
+  if (spt) spt->assign(n, std::vector<DecodedPiece>());
+  DecodePath path = decode_path_ != kDecodeAuto ? decode_path_ : DecodePathFromEnv();
+  if (path == kDecodeAuto) path = tokens >= kDecodeDeviceMinTokens ? kDecodeDevice : kDecodeHost;
+  std::vector<char> done(n, 0);
+  if (path == kDecodeDevice) {
+    // Every line whose pieces are all in the vocabulary goes up as one id CSR.
+    std::vector<size_t> lines;
+    std::vector<int32_t> ids;
+    std::vector<uint64_t> off(1, 0);
+    Status st = Status::Ok();
+    uint64_t extras = 0;
+    for (const ExtraOption o : decode_extra_) extras += o != REVERSE;
+    for (size_t i = 0; i < n; ++i) {
+      if (oov[i]) continue;
+      lines.push_back(i);
+      for (const auto &pi : (*rows)[i]) ids.push_back(pi.second);
+      off.push_back(ids.size());
+    }
+    const uint64_t nd = lines.size();
+    if (nd) {
+      std::vector<uint64_t> out_off(nd + 1);
+      uint64_t total = 0;
+      // Size the text by the model's bound when that stays small, else by a
+      // count call: a batch that large amortizes it, and tokens * bound would
+      // be many times the text.
+      uint32_t bound = 0;
+      st = FromC(spm_hip_model_decode_bound(model_, &bound));
+      if (!st.ok()) return st;
+      total = (ids.size() + nd * extras) * static_cast<uint64_t>(bound);
+      if (total > (16u << 20)) {
+        st = FromC(spm_hip_decode_batch_host(model_, decode_extra_str_.c_str(), ids.data(), off.data(), nd, nullptr,
+                                             0, out_off.data(), nullptr, &total));
+        if (!st.ok()) return st;
+      }
+      std::string out(total, '\0');
+      std::vector<uint32_t> begins(spt ? ids.size() + nd * extras : 0);
+      st = FromC(spm_hip_decode_batch_host(model_, decode_extra_str_.c_str(), ids.data(), off.data(), nd,
+                                           reinterpret_cast<uint8_t *>(&out[0]), out.size(), out_off.data(),
+                                           spt ? begins.data() : nullptr, &total));
+      if (!st.ok()) return st;
+      uint64_t g = 0;
+      for (uint64_t k = 0; k < nd; ++k) {
+        const size_t i = lines[k];
+        std::string &text = (*texts)[i];
+        text.assign(out, out_off[k], out_off[k + 1] - out_off[k]);
+        done[i] = 1;
+        if (!spt) continue;
+        auto &row = (*rows)[i];
+        DecodeLineHost(&row, nullptr, nullptr);  // the piece list in final order
+        auto &dst = (*spt)[i];
+        dst.resize(row.size());
+        for (size_t t = 0; t < row.size(); ++t, ++g) {
+          DecodedPiece &d = dst[t];
+          d.piece = row[t].first;
+          d.id = row[t].second;
+          d.begin = begins[g];
+          d.end = t + 1 < row.size() ? begins[g + 1] : static_cast<uint32_t>(text.size());
+          d.surface.assign(text, d.begin, d.end - d.begin);
+        }
+      }
+    }
+  }
+  for (size_t i = 0; i < n; ++i)
+    if (!done[i]) DecodeLineHost(&(*rows)[i], &(*texts)[i], spt ? &(*spt)[i] : nullptr);
+  return Status::Ok();
+}
+
+Status SentencePieceProcessor::DecodeBatch(const std::vector<std::vector<int>> &ids, std::vector<std::string> *texts,
+                                           std::vector<std::vector<DecodedPiece>> *spt) const {
+  if (!status_.ok()) return status_;
+  if (!texts) return Err(SPM_INTERNAL, "output container is null");
+  texts->clear();
+  std::vector<std::vector<std::pair<std::string, int>>> rows(ids.size());
+  for (size_t i = 0; i < ids.size(); ++i) {
+    rows[i].reserve(ids[i].size());
+    for (const int id : ids[i]) {
+      const bool in_range = id >= 0 && id < GetPieceSize();  // DecodeRows rejects the others
+      rows[i].emplace_back(IdToPiece(id), in_range ? PieceToId(IdToPiece(id)) : id);
+    }
+  }
+  return DecodeRows(&rows, std::vector<char>(ids.size(), 0), texts, spt);
+}
+
+Status SentencePieceProcessor::DecodeBatch(const std::vector<std::vector<std::string>> &pieces,
+                                           std::vector<std::string> *texts,
+                                           std::vector<std::vector<DecodedPiece>> *spt) const {
+  if (!status_.ok()) return status_;
+  if (!texts) return Err(SPM_INTERNAL, "output container is null");
+  texts->clear();
+  std::vector<std::vector<std::pair<std::string, int>>> rows(pieces.size());
+  std::vector<char> oov(pieces.size(), 0);
+  for (size_t i = 0; i < pieces.size(); ++i) {
+    rows[i].reserve(pieces[i].size());
+    for (const std::string &w : pieces[i]) {
+      const int id = PieceToId(w);
+      if (IsUnknown(id) && IdToPiece(id) != w) oov[i] = 1;
+      rows[i].emplace_back(w, id);
+    }
+  }
+  return DecodeRows(&rows, oov, texts, spt);
+}
+
+Status SentencePieceProcessor::Decode(const std::vector<int> &ids, std::string *detokenized) const {
+  if (!status_.ok()) return status_;
+  if (!detokenized) return Err(SPM_INTERNAL, "output container is null");
+  detokenized->clear();
+  std::vector<std::string> out;
+  Status st = DecodeBatch(std::vector<std::vector<int>>{ids}, &out);
+  if (st.ok()) *detokenized = std::move(out[0]);
+  return st;
+}
+
+Status SentencePieceProcessor::Decode(const std::vector<std::string> &pieces, std::string *detokenized) const {
+  if (!status_.ok()) return status_;
+  if (!detokenized) return Err(SPM_INTERNAL, "output container is null");
+  detokenized->clear();
+  std::vector<std::string> out;
+  Status st = DecodeBatch(std::vector<std::vector<std::string>>{pieces}, &out);
+  if (st.ok()) *detokenized = std::move(out[0]);
   return st;
 }
 

@@ -4,7 +4,9 @@
 // Same names, argument meaning and error behaviour as the reference for the
 // calls on the hot path: Load / LoadFromSerializedProto, SetEncodeExtraOptions,
 // Encode(ids), Encode(pieces), PieceToId / IdToPiece / GetPieceSize /
-// IsUnknown / IsControl / unk_id / bos_id / eos_id / pad_id.  Encode is
+// IsUnknown / IsControl / unk_id / bos_id / eos_id / pad_id, and for the way
+// back: SetDecodeExtraOptions, Decode(ids), Decode(pieces) and their batched
+// form DecodeBatch (spm_hip_decode_batch on the device).  Encode is
 // batched: EncodeBatch runs the device normalizer and the device encode over
 // the whole batch; Encode(ids) also runs the id epilogue of
 // PopulateSentencePieceText (unk merge, control pieces) + ApplyExtraOptions
@@ -86,6 +88,42 @@ class SentencePieceProcessor {
                           std::vector<std::vector<std::vector<std::string>>> *pieces,
                           std::vector<std::vector<float>> *scores) const;
 
+  // Decode (sentencepiece_processor.cc:341-370, :670-733).  One piece of
+  // SentencePieceText: surface = text[begin, end).
+  struct DecodedPiece {
+    std::string piece;
+    int id = 0;
+    std::string surface;
+    uint32_t begin = 0, end = 0;
+  };
+  // "bos", "eos", "reverse" separated by ':', applied to the piece list in
+  // the order given (ParseExtraOptions :981-1023, ApplyExtraOptions :945-979).
+  Status SetDecodeExtraOptions(const std::string &extra_options);
+  Status Decode(const std::vector<int> &ids, std::string *detokenized) const;
+  Status Decode(const std::vector<std::string> &pieces, std::string *detokenized) const;
+  // Batched: texts[i] is the text of line i; spt (may be null) receives every
+  // line's pieces in final order with their surfaces.  Batches of at least
+  // kDecodeDeviceMinTokens tokens run on the device in one call
+  // (spm_hip_decode_batch); smaller ones, and every line that holds a piece
+  // outside the vocabulary (its own bytes are its surface), run the same
+  // rules in a loop on the host.  Unlike the reference, which indexes the
+  // piece table unchecked, an id outside [0, GetPieceSize()) is
+  // SPM_OUT_OF_RANGE.
+  Status DecodeBatch(const std::vector<std::vector<int>> &ids, std::vector<std::string> *texts,
+                     std::vector<std::vector<DecodedPiece>> *spt = nullptr) const;
+  Status DecodeBatch(const std::vector<std::vector<std::string>> &pieces, std::vector<std::string> *texts,
+                     std::vector<std::vector<DecodedPiece>> *spt = nullptr) const;
+  // Where DecodeBatch runs: kDecodeAuto picks by the batch's token count.
+  // SPM_HIP_DECODE_PATH=host|device sets the initial value.
+  enum DecodePath { kDecodeAuto = 0, kDecodeHost = 1, kDecodeDevice = 2 };
+  void SetDecodePath(DecodePath path) { decode_path_ = path; }
+  // Token count from which the device call (upload, decode, download) beats
+  // the host loop.  Measured by tools/decode_bench.py on the c2 ids
+  // (profiles/pr13_decode.txt): at 17493 tokens the host loop takes 0.135 ms
+  // and the device call 0.157 ms, at 70100 tokens 0.672 ms against 0.199 ms;
+  // the lines cross near 21 k tokens, and the next power of two is used.
+  static constexpr uint64_t kDecodeDeviceMinTokens = 32768;
+
   int GetPieceSize() const;
   int PieceToId(const std::string &piece) const;
   const std::string &IdToPiece(int id) const;
@@ -105,6 +143,16 @@ class SentencePieceProcessor {
   std::unordered_map<std::string, int> pieces_, reserved_;
   std::vector<ExtraOption> extra_;
   std::string extra_str_;  // the accepted option string, for the device epilogue
+  std::vector<ExtraOption> decode_extra_;
+  std::string decode_extra_str_;
+  DecodePath decode_path_ = kDecodeAuto;
+  Status ParseExtraOptions(const std::string &opts, std::vector<ExtraOption> *out) const;
+  // One line's (piece, id) list -> options applied, text and pieces.
+  void DecodeLineHost(std::vector<std::pair<std::string, int>> *row, std::string *text,
+                      std::vector<DecodedPiece> *spt) const;
+  // rows[i]: line i as (piece, id); oov[i]: it holds a piece outside the vocabulary.
+  Status DecodeRows(std::vector<std::vector<std::pair<std::string, int>>> *rows, const std::vector<char> &oov,
+                    std::vector<std::string> *texts, std::vector<std::vector<DecodedPiece>> *spt) const;
   Status status_{SPM_INTERNAL, "Model is not initialized."};
   // Sampler: the seed and the number of lines sampled so far (the next
   // call's index_base).

@@ -774,6 +774,57 @@ int EnsureNormTables(spm_hip_model *m) {
   return SPM_OK;
 }
 
+// The decode table (decode.h) of SentencePieceProcessor::Decode
+// (sentencepiece_processor.cc:670-716).  Decode(ids) maps an id to its piece
+// and the piece back to an id (PieceToId: reserved pieces first), so the type
+// that decides the surface is that of PieceToId(IdToPiece(id)).
+int BuildDecodeTable(spm_hip_model *m) {
+  static const char kSpace[] = "\xE2\x96\x81";  // U+2581
+  const auto &ts = m->proto.trainer_spec;
+  const std::string unk_surface = ts.has_unk_surface ? ts.unk_surface : std::string(" \xE2\x81\x87 ");
+  spm_amd::DecodeTable &t = m->decode;
+  const size_t v = m->proto.pieces.size();
+  t.meta.assign(v, 0);
+  t.off.assign(v, 0);
+  t.bytes.clear();
+  t.max_surface = 0;
+  for (size_t i = 0; i < v; ++i) {
+    const std::string &piece = m->proto.pieces[i].piece;
+    int32_t id = static_cast<int32_t>(i);
+    auto r = m->reserved.find(piece);
+    if (r != m->reserved.end()) id = r->second;
+    const int32_t type = m->proto.pieces[id].type;
+    std::string surface;
+    uint32_t strip = 0;
+    if (type == spm_amd::kControl) {
+    } else if (type == spm_amd::kUnknown) {
+      surface = unk_surface;
+    } else {
+      strip = piece.compare(0, 3, kSpace) == 0 ? 1u : 0u;
+      for (size_t k = 0; k < piece.size();) {
+        if (piece.compare(k, 3, kSpace) == 0) {
+          surface.push_back(' ');
+          k += 3;
+        } else {
+          surface.push_back(piece[k++]);
+        }
+      }
+    }
+    if (surface.size() > spm_amd::kDecodeMaxSurface || t.bytes.size() + surface.size() > 0x7FFFFFFFull)
+      return Fail(SPM_OUT_OF_RANGE, "piece surfaces too large for the decode table");
+    t.off[i] = static_cast<uint32_t>(t.bytes.size());
+    t.meta[i] = (static_cast<uint32_t>(surface.size()) << 1) | strip;
+    t.bytes.insert(t.bytes.end(), surface.begin(), surface.end());
+    t.max_surface = std::max<uint32_t>(t.max_surface, static_cast<uint32_t>(surface.size()));
+  }
+  if (!m->host_only) {
+    SPM_HIP_TRY(Upload(&m->d_dec_meta, t.meta));
+    SPM_HIP_TRY(Upload(&m->d_dec_off, t.off));
+    SPM_HIP_TRY(Upload(&m->d_dec_bytes, t.bytes));
+  }
+  return SPM_OK;
+}
+
 // Lazy per-piece type bits of the id epilogue.
 int EnsureTypes(spm_hip_model *m) {
   if (m->types_ready) return SPM_OK;
@@ -897,7 +948,7 @@ void EncodeWorkspace::Release() {
   if (svc_prof) (void)spm_amd::DevFree(svc_prof);
   svc_prof = nullptr;
   for (DevBuf *b : {&w_ctl, &w_slot_ids, &w_slot_len, &w_tprefix, &w_slot2_ids, &w_slot2_len, &w_ntok, &w_cnt, &w_bp, &w_flagged, &w_ovf, &w_scan,
-                    &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_tids, &w_tlen, &w_ttok,
+                    &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_dfirst, &w_dsum, &w_dctl, &h_dids, &h_dtok, &h_dout, &h_doff, &h_dbegin, &w_tids, &w_tlen, &w_ttok,
                     &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask,
                     &w_nb_ctl, &w_nb_npaths, &w_nb_stage, &w_nb_ntok, &w_nb_score, &w_nb_ids, &w_nb_len, &w_nb_hids,
                     &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore})
@@ -1061,6 +1112,7 @@ static int LoadImpl(const void *model_proto, size_t len, spm_hip_model **out, bo
     else if (m->model_type == spm_amd::kBpe) rc = spm_amd::LoadBpe(m, &g_last_error);
     else rc = Fail(SPM_UNIMPLEMENTED, "only unigram and bpe models run on the device");
   }
+  if (rc == SPM_OK) rc = BuildDecodeTable(m);
   if (rc != SPM_OK) {
     spm_hip_model_free(m);
     return rc;
@@ -1120,7 +1172,7 @@ void spm_hip_model_free(spm_hip_model *m) {
   for (spm_amd::DevBuf *b : {&m->d_units, &m->d_uvs, &m->d_piece_tab, &m->d_values, &m->d_scores,
                              &m->bpe.pair_keys, &m->bpe.pair_vals, &m->bpe.pair_ent, &m->bpe.rank_piece, &m->bpe.entry_piece,
                              &m->bpe.entry_out, &m->bpe.piece_kind, &m->bpe.piece_out,
-                             &m->d_charsmap, &m->d_ud_units, &m->d_types})
+                             &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes})
     b->Release();
   for (auto &kv : m->by_stream) kv.second->Release();
   for (auto &w : m->host_pool) w->Release();
@@ -2740,6 +2792,168 @@ int spm_hip_nbest_last_stats(const spm_hip_model *m, uint64_t *second_pass, uint
 int spm_hip_sample_uniform(uint64_t seed, uint64_t index, uint64_t draw, double *u) {
   if (!u) return Fail(SPM_INVALID_ARGUMENT, "null argument");
   *u = spm_amd::SampleDraw(spm_amd::SampleKey(seed, index), draw);
+  return SPM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Decode (sentencepiece_processor.cc:670-733) on the device: decode_kernels.hip.
+namespace {
+
+int FailDecodeRange(uint64_t sentence, int64_t id, size_t pieces) {
+  return Fail(SPM_OUT_OF_RANGE, "decode: sentence " + std::to_string(sentence) + " holds id " + std::to_string(id) +
+                                    ", outside [0, " + std::to_string(pieces) + ")");
+}
+
+int DecodeImpl(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd::EpilogueExtras &x,
+               const int32_t *d_ids, const uint64_t *d_tok_off, uint64_t n, uint8_t *d_out, uint64_t out_capacity,
+               uint64_t *d_out_off, uint32_t *d_piece_begin, uint64_t *total, uint32_t *chain, hipStream_t st) {
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  if (n == 0) {
+    SPM_HIP_TRY(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), st));
+    if (total) *total = 0;
+    return SPM_OK;
+  }
+  SPM_HIP_TRY(ws->w_dfirst.Reserve(n * sizeof(uint32_t)));
+  SPM_HIP_TRY(ws->w_dsum.Reserve(spm_amd::kDecodeBlocks * sizeof(uint64_t)));
+  SPM_HIP_TRY(ws->w_dctl.Reserve(spm_amd::kDcWords * sizeof(uint64_t)));
+  uint64_t *ctl = ws->w_dctl.as<uint64_t>();
+  SPM_HIP_TRY(hipMemsetAsync(ctl, 0, spm_amd::kDcWords * sizeof(uint64_t), st));
+  SPM_HIP_TRY(hipMemsetAsync(ctl + spm_amd::kDcBadKey, 0xFF, sizeof(uint64_t), st));
+  SPM_HIP_TRY(hipMemsetAsync(ws->w_dfirst.ptr, 0xFF, n * sizeof(uint32_t), st));
+  spm_amd::DecodeLaunch a{};
+  a.ids = d_ids;
+  a.tok_off = d_tok_off;
+  a.n = n;
+  a.meta = m->d_dec_meta.as<uint32_t>();
+  a.off = m->d_dec_off.as<uint32_t>();
+  a.bytes = m->d_dec_bytes.as<uint8_t>();
+  a.num_pieces = static_cast<int32_t>(m->decode.meta.size());
+  a.x = x;
+  a.first = ws->w_dfirst.as<uint32_t>();
+  a.block_sum = ws->w_dsum.as<uint64_t>();
+  a.ctl = ctl;
+  // Blocking call: the call's own status word lives in the control block.
+  a.chain = chain ? chain : reinterpret_cast<uint32_t *>(ctl + spm_amd::kDcStatus);
+  a.out = d_out;
+  a.capacity = out_capacity;
+  a.out_off = d_out_off;
+  a.piece_begin = d_piece_begin;
+  SPM_HIP_TRY(spm_amd::LaunchDecode(a, chain == nullptr, st));
+  if (chain) return SPM_OK;
+  uint64_t h[spm_amd::kDcWords];
+  static_assert(sizeof(h) <= 48, "read-back fits the pinned slots below the epilogue's");
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, ctl, sizeof(h), hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(h, ws->pinned, sizeof(h));
+  const uint32_t status = static_cast<uint32_t>(h[spm_amd::kDcStatus]);
+  if (status == SPM_OUT_OF_RANGE)
+    return FailDecodeRange(h[spm_amd::kDcBadSentence], static_cast<int64_t>(h[spm_amd::kDcBadId]),
+                           m->decode.meta.size());
+  if (total) *total = h[spm_amd::kDcTotal];
+  if (status == SPM_RESOURCE_EXHAUSTED) return Fail(SPM_RESOURCE_EXHAUSTED, "decoded text exceeds out_capacity");
+  if (status != 0) return Fail(static_cast<int>(status), "decode failed");
+  return SPM_OK;
+}
+
+int DecodeArgs(spm_hip_model *m, const char *extra_options, const uint64_t *tok_off, uint64_t *out_off,
+               spm_amd::EpilogueExtras *x) {
+  if (!m || !tok_off || !out_off) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (m->decode.meta.empty()) return Fail(SPM_FAILED_PRECONDITION, "model has no decode table");
+  return FoldExtras(m, extra_options, x);
+}
+
+}  // namespace
+
+int spm_hip_decode_batch(spm_hip_model *m, const char *extra_options, const int32_t *d_ids,
+                         const uint64_t *d_tok_off, uint64_t n, uint8_t *d_out, uint64_t out_capacity,
+                         uint64_t *d_out_off, uint32_t *d_piece_begin, uint64_t *total, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_decode_batch");
+  spm_amd::EpilogueExtras x{};
+  const int rc = DecodeArgs(m, extra_options, d_tok_off, d_out_off, &x);
+  if (rc != SPM_OK) return rc;
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForStream(m, st));
+  return DecodeImpl(m, ws.get(), x, d_ids, d_tok_off, n, d_out, out_capacity, d_out_off, d_piece_begin, total,
+                    nullptr, st);
+}
+
+int spm_hip_decode_batch_async(spm_hip_model *m, const char *extra_options, const int32_t *d_ids,
+                               const uint64_t *d_tok_off, uint64_t n, uint8_t *d_out, uint64_t out_capacity,
+                               uint64_t *d_out_off, uint32_t *d_piece_begin, uint32_t *d_status, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_decode_batch_async");
+  if (!d_status) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  spm_amd::EpilogueExtras x{};
+  const int rc = DecodeArgs(m, extra_options, d_tok_off, d_out_off, &x);
+  if (rc != SPM_OK) return rc;
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForStream(m, st));
+  return DecodeImpl(m, ws.get(), x, d_ids, d_tok_off, n, d_out, out_capacity, d_out_off, d_piece_begin, nullptr,
+                    d_status, st);
+}
+
+int spm_hip_decode_batch_host(spm_hip_model *m, const char *extra_options, const int32_t *ids,
+                              const uint64_t *tok_off, uint64_t n, uint8_t *out, uint64_t out_capacity,
+                              uint64_t *out_off, uint32_t *piece_begin, uint64_t *total) {
+  spm_amd::TraceRange trace_range_("spm_hip_decode_batch_host");
+  spm_amd::EpilogueExtras x{};
+  int rc = DecodeArgs(m, extra_options, tok_off, out_off, &x);
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  if (tok_off[0] != 0) return Fail(SPM_INVALID_ARGUMENT, "offsets must start at 0");
+  for (uint64_t i = 0; i < n; ++i)
+    if (tok_off[i + 1] < tok_off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
+  const uint64_t tokens = tok_off[n];
+  if (tokens && !ids) return Fail(SPM_INVALID_ARGUMENT, "null ids");
+  if (total) *total = 0;
+  if (m->host_only) {
+    uint64_t bad_sentence = 0;
+    int32_t bad_id = 0;
+    // Offsets go to a scratch first: an out-of-range id must leave no output.
+    std::vector<uint64_t> off(n + 1);
+    rc = spm_amd::DecodeHostLoop(m->decode, x, ids, tok_off, n, out, out_capacity, off.data(), piece_begin,
+                                 &bad_sentence, &bad_id);
+    if (rc != SPM_OK) return FailDecodeRange(bad_sentence, bad_id, m->decode.meta.size());
+    std::memcpy(out_off, off.data(), (n + 1) * sizeof(uint64_t));
+    if (total) *total = off[n];
+    if (out && off[n] > out_capacity) return Fail(SPM_RESOURCE_EXHAUSTED, "decoded text exceeds out_capacity");
+    return SPM_OK;
+  }
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForHost(m));
+  hipStream_t st = ws.stream();
+  const uint64_t final_tokens = tokens + n * (x.num_pre + x.num_post);
+  SPM_HIP_TRY(ws->h_dids.Reserve(std::max<uint64_t>(tokens, 1) * sizeof(int32_t)));
+  SPM_HIP_TRY(ws->h_dtok.Reserve((n + 1) * sizeof(uint64_t)));
+  SPM_HIP_TRY(ws->h_doff.Reserve((n + 1) * sizeof(uint64_t)));
+  if (out) SPM_HIP_TRY(ws->h_dout.Reserve(std::max<uint64_t>(out_capacity, 1)));
+  if (out && piece_begin) SPM_HIP_TRY(ws->h_dbegin.Reserve(std::max<uint64_t>(final_tokens, 1) * sizeof(uint32_t)));
+  if (tokens) SPM_HIP_TRY(hipMemcpyAsync(ws->h_dids.ptr, ids, tokens * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->h_dtok.ptr, tok_off, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  uint64_t tot = 0;
+  rc = DecodeImpl(m, ws.get(), x, ws->h_dids.as<int32_t>(), ws->h_dtok.as<uint64_t>(), n,
+                  out ? ws->h_dout.as<uint8_t>() : nullptr, out_capacity, ws->h_doff.as<uint64_t>(),
+                  out && piece_begin ? ws->h_dbegin.as<uint32_t>() : nullptr, &tot, nullptr, st);
+  if (rc != SPM_OK && rc != SPM_RESOURCE_EXHAUSTED) return rc;
+  if (total) *total = tot;
+  SPM_HIP_TRY(hipMemcpyAsync(out_off, ws->h_doff.ptr, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  if (rc == SPM_OK && out) {
+    if (tot) SPM_HIP_TRY(hipMemcpyAsync(out, ws->h_dout.ptr, tot, hipMemcpyDeviceToHost, st));
+    if (piece_begin && final_tokens)
+      SPM_HIP_TRY(hipMemcpyAsync(piece_begin, ws->h_dbegin.ptr, final_tokens * sizeof(uint32_t),
+                                 hipMemcpyDeviceToHost, st));
+  }
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  return rc;
+}
+
+int spm_hip_model_decode_bound(const spm_hip_model *m, uint32_t *max_surface_bytes) {
+  if (!m || !max_surface_bytes) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (m->decode.meta.empty()) return Fail(SPM_FAILED_PRECONDITION, "model has no decode table");
+  *max_surface_bytes = m->decode.max_surface;
   return SPM_OK;
 }
 

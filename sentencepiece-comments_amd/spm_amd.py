@@ -16,12 +16,17 @@ LIB_PATH = os.environ.get("SPM_AMD_LIB") or os.path.join(HERE, "lib", "libspm_hi
 
 SPM_OK = 0
 SPM_RESOURCE_EXHAUSTED = 8
+SPM_OUT_OF_RANGE = 11
+# Decode kernels (csrc/decode.h): tokens per tile, per sub-tile (one block
+# scan) and the block count of a token pass.
+DECODE_TILE_TOKENS, DECODE_SUBTILE_TOKENS, DECODE_BLOCKS = 1024, 256, 1024
 SPM_UNIGRAM, SPM_BPE = 1, 2
 SPM_ESTEP_FAST, SPM_ESTEP_PARITY = 0, 1
 SPM_ESTEP_DEFER_FOLD = 0x100  # include/spm_hip.h
 
 # Every symbol include/spm_hip.h declares.
 EXPORTED = [
+    "spm_hip_decode_batch", "spm_hip_decode_batch_async", "spm_hip_decode_batch_host", "spm_hip_model_decode_bound",
     "spm_hip_model_load", "spm_hip_model_load_host_only", "spm_hip_model_free", "spm_hip_model_get_info",
     "spm_hip_encode_batch", "spm_hip_encode_batch_host", "spm_hip_normalize_batch",
     "spm_hip_model_set_force_general", "spm_hip_model_set_timing", "spm_hip_model_last_stats",
@@ -209,6 +214,10 @@ def lib():
         L.spm_hip_model_set_nbest_max_hyps.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32]
         L.spm_hip_nbest_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_device_peak_reset.restype = None
+        L.spm_hip_decode_batch.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, ctypes.POINTER(U64), P]
+        L.spm_hip_decode_batch_async.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, P, P]
+        L.spm_hip_decode_batch_host.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, ctypes.POINTER(U64)]
+        L.spm_hip_model_decode_bound.argtypes = [P, ctypes.POINTER(ctypes.c_uint32)]
         _lib = L
     return _lib
 
@@ -612,6 +621,63 @@ class DeviceModel:
                                             out_capacity, ctypes.c_void_p(d_out_off), ctypes.byref(tot),
                                             ctypes.c_void_p(stream) if stream else None))
         return tot.value
+
+    def decode_bound(self):
+        """spm_hip_model_decode_bound: the longest surface of any id, in bytes."""
+        b = ctypes.c_uint32()
+        _check(self._L.spm_hip_model_decode_bound(self.h, ctypes.byref(b)))
+        return b.value
+
+    def decode_device(self, extra_options, d_ids, d_tok, n, d_out, out_capacity, d_out_off, d_piece_begin=None,
+                      stream=None):
+        """spm_hip_decode_batch on device pointers (d_out 0/None: count only);
+        returns the text's byte count.  RESOURCE_EXHAUSTED raises SpmError
+        with the count in its `total` attribute."""
+        V = ctypes.c_void_p
+        tot = ctypes.c_uint64()
+        rc = self._L.spm_hip_decode_batch(self.h, extra_options.encode(), V(d_ids), V(d_tok), n,
+                                          V(d_out) if d_out else None, out_capacity, V(d_out_off),
+                                          V(d_piece_begin) if d_piece_begin else None, ctypes.byref(tot),
+                                          V(stream) if stream else None)
+        if rc != SPM_OK:
+            err = SpmError(rc, self._L.spm_hip_last_error().decode(errors="replace"))
+            err.total = tot.value
+            raise err
+        return tot.value
+
+    def decode_device_async(self, extra_options, d_ids, d_tok, n, d_out, out_capacity, d_out_off, d_status,
+                            d_piece_begin=None, stream=None):
+        """spm_hip_decode_batch_async: pure stream call; failures land in the
+        device status word d_status, the byte count in d_out_off[n]."""
+        V = ctypes.c_void_p
+        _check(self._L.spm_hip_decode_batch_async(self.h, extra_options.encode(), V(d_ids), V(d_tok), n,
+                                                  V(d_out) if d_out else None, out_capacity, V(d_out_off),
+                                                  V(d_piece_begin) if d_piece_begin else None, V(d_status),
+                                                  V(stream) if stream else None))
+
+    def decode_csr_host(self, ids, tok_off, extra_options="", with_begin=False, capacity=None):
+        """spm_hip_decode_batch_host: host id CSR in -> (text bytes uint8,
+        out_off uint64[n+1], [piece_begin uint32]).  Works on a host-only
+        model (plain loop, no GPU).  capacity None: sized by a count call."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+        n = len(tok_off) - 1
+        oo = np.zeros(n + 1, dtype=np.uint64)
+        tot = ctypes.c_uint64()
+        eo = extra_options.encode()
+        idp = _p(ids) if ids.size else None
+        if capacity is None:
+            _check(self._L.spm_hip_decode_batch_host(self.h, eo, idp, _p(tok_off), n, None, 0, _p(oo), None,
+                                                     ctypes.byref(tot)))
+            capacity = tot.value
+        out = np.zeros(max(capacity, 1), dtype=np.uint8)
+        n_extra = sum(1 for o in extra_options.split(":") if o in ("bos", "eos"))
+        begin = np.zeros(max(int(tok_off[-1]) + n * n_extra, 1), dtype=np.uint32) if with_begin else None
+        _check(self._L.spm_hip_decode_batch_host(self.h, eo, idp, _p(tok_off), n, _p(out), capacity, _p(oo),
+                                                 _p(begin) if with_begin else None, ctypes.byref(tot)))
+        if with_begin:
+            return out[:tot.value], oo, begin[:int(tok_off[-1]) + n * n_extra]
+        return out[:tot.value], oo
 
     def encode_raw_small(self, lines):
         """spm_hip_encode_raw_small_host: raw lines -> final ids (Encode(line,
