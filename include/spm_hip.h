@@ -576,7 +576,9 @@ int spm_hip_estep_kernel_times(spm_hip_pieces *pieces, double *forward_ms, doubl
  * keep, 0 = not, 2 = the search outgrew the device slab (caller re-runs that
  * piece on the host); d_alt at d_alt_off[i] (capacity: the piece's char
  * count) receives d_alt_n[i] ids of the second-best path when d_keep[i] == 1
- * (the reference's `alternatives`). */
+ * (the reference's `alternatives`).  The slab holds 4096 hypotheses per
+ * piece; the environment variable SPM_HIP_PRUNE_MAX_HYPS (tests; clamped to
+ * [2, 4096]) lowers the count at which a piece is flagged 2. */
 int spm_hip_prune_nbest(spm_hip_pieces *pieces, const uint8_t *d_piece_bytes,
                         const uint64_t *d_piece_off, uint8_t *d_keep, int32_t *d_alt,
                         const uint64_t *d_alt_off, uint32_t *d_alt_n, uint32_t max_piece_bytes,

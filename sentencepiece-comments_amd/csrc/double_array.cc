@@ -161,9 +161,25 @@ class Placer {
 
 namespace {
 
-// Keys in build order: NUL-truncated, sorted by bytes, the first value of
-// equal keys kept, empty keys dropped.
+// Keys in build order: NUL-truncated, sorted by bytes, one value of equal
+// keys kept, empty keys dropped.  Keys that are equal only after the
+// truncation keep the value of the one that sorts first as a whole string, as
+// the reference's BuildTrie does (it sorts the whole strings and darts-clone
+// keeps the first insert of a C string); equal whole strings keep the first
+// listed.  (The reference's pair sort would order those by value; every caller
+// lists its keys with values ascending, where the two rules agree.)
 void Canonicalize(std::vector<std::pair<std::string, int32_t>> *keys) {
+  bool has_nul = false;
+  for (const auto &k : *keys)
+    if (k.first.find('\0') != std::string::npos) {
+      has_nul = true;
+      break;
+    }
+  if (has_nul)
+    std::stable_sort(keys->begin(), keys->end(),
+                     [](const std::pair<std::string, int32_t> &a, const std::pair<std::string, int32_t> &b) {
+                       return a.first < b.first;
+                     });
   for (auto &k : *keys) {
     const size_t z = k.first.find('\0');
     if (z != std::string::npos) k.first.resize(z);

@@ -41,8 +41,9 @@ struct DoubleArray {
                           std::vector<std::pair<int32_t, size_t>> *out) const;
 };
 
-// keys: (bytes, value).  Duplicate keys (after NUL truncation) keep the first
-// value.  Returns false if the array would exceed kBaseLimit units.
+// keys: (bytes, value).  Of keys equal after NUL truncation, the one that
+// sorts first as a whole string keeps its value (equal strings: the first).
+// Returns false if the array would exceed kBaseLimit units.
 bool BuildDoubleArray(std::vector<std::pair<std::string, int32_t>> keys, DoubleArray *out,
                       std::string *err);
 

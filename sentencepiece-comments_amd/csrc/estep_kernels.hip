@@ -52,6 +52,7 @@
 #include "device_common.h"
 #include "device_model.h"
 #include "double_array.h"
+#include "host_prune_nbest.h"
 #include "kernels.h"
 #include "normalizer.h"
 #include "trace.h"
@@ -1803,7 +1804,8 @@ __global__ void estep_finalize_kernel(int mode, int T, uint64_t V, const double 
 // agenda as a binary heap with libstdc++'s push_heap / pop_heap moves
 // (std::priority_queue<Hypothesis*> ordered by fx <) so equal-fx hypotheses
 // pop in the reference's order.  A piece whose hypotheses outgrow the slab is
-// flagged (keep = 2) for the host path.
+// flagged (keep = 2) for the host path.  Lanes [0, lanes) take pieces, lane t
+// on slab t (PlanPruneNBest, host_prune_nbest.h); a lane past them does nothing.
 // ---------------------------------------------------------------------------
 struct NBestArgs {
   const uint8_t *__restrict__ bytes;
@@ -1816,6 +1818,7 @@ struct NBestArgs {
   float unk_score;
   uint8_t *__restrict__ scratch;
   uint64_t slab_bytes;
+  uint64_t lanes;
   uint32_t max_nb;
   int K;
   uint32_t max_hyps;
@@ -1825,15 +1828,10 @@ struct NBestArgs {
   uint32_t *__restrict__ alt_n;
 };
 
-uint64_t NBestSlab(uint32_t nb, int K, uint32_t max_hyps) {
-  const uint64_t cap = static_cast<uint64_t>(nb) * K + 2;
-  return ((static_cast<uint64_t>(nb) + 1) * 5 + cap * 7 + static_cast<uint64_t>(max_hyps) * 5) * 4 + 64;
-}
-
 __global__ __launch_bounds__(64) void prune_nbest_kernel(NBestArgs g) {
   const uint64_t tid = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  const uint64_t nthreads = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-  for (uint64_t i = tid; i < g.V; i += nthreads) {
+  if (tid >= g.lanes) return;
+  for (uint64_t i = tid; i < g.V; i += g.lanes) {
     const uint64_t b0 = g.off[i];
     const uint32_t nb = static_cast<uint32_t>(g.off[i + 1] - b0);
     g.alt_n[i] = 0;
@@ -2737,17 +2735,19 @@ int spm_hip_prune_nbest(spm_hip_pieces *P, const uint8_t *d_piece_bytes, const u
     return SPM_INVALID_ARGUMENT;
   std::lock_guard<std::recursive_mutex> lock(P->mu);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  constexpr uint32_t kMaxHyps = 4096;
+  // SPM_HIP_PRUNE_MAX_HYPS (tests): fewer hypotheses per piece before the
+  // search is handed to the host; the slab stays sized for the default.
+  uint32_t max_hyps = kPruneNBestMaxHyps;
+  if (const char *e = std::getenv("SPM_HIP_PRUNE_MAX_HYPS"))
+    max_hyps = static_cast<uint32_t>(std::min<long>(std::max<long>(std::atol(e), 2), kPruneNBestMaxHyps));
   const int K = P->trie_results_size + 1;
   const uint32_t max_nb = std::max<uint32_t>(max_piece_bytes, 1);
-  const uint64_t slab = NBestSlab(max_nb, K, kMaxHyps);
-  uint64_t threads = std::min<uint64_t>(std::max<uint64_t>(P->V, 1), 16384);
-  while (threads > 64 && threads * slab > (1ull << 30)) threads /= 2;
-  E_TRY(P->w_scratch.Reserve(threads * slab));
+  const PruneNBestPlan plan = PlanPruneNBest(P->V, max_nb, K);
+  E_TRY(P->w_scratch.Reserve(plan.reserve_bytes));
   NBestArgs g{d_piece_bytes, d_piece_off, P->V, P->d_units.as<uint32_t>(), P->d_values.as<int32_t>(),
-              P->d_scores.as<float>(), P->root_base, P->unk_score, P->w_scratch.as<uint8_t>(), slab,
-              max_nb, K, kMaxHyps, d_keep, d_alt, d_alt_off, d_alt_n};
-  hipLaunchKernelGGL(prune_nbest_kernel, dim3(static_cast<unsigned>((threads + 63) / 64)), dim3(64), 0, st, g);
+              P->d_scores.as<float>(), P->root_base, P->unk_score, P->w_scratch.as<uint8_t>(), plan.slab_bytes,
+              plan.lanes, max_nb, K, max_hyps, d_keep, d_alt, d_alt_off, d_alt_n};
+  hipLaunchKernelGGL(prune_nbest_kernel, dim3(plan.grid), dim3(kPruneNBestBlock), 0, st, g);
   E_TRY(hipGetLastError());
   return SPM_OK;
 }

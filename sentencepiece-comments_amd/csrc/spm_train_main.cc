@@ -145,7 +145,7 @@ int main(int argc, char **argv) {
         "\"bpe_updates\": %llu, \"bpe_update_replays\": %llu, \"bpe_refresh_device_ms\": %.3f, "
         "\"bpe_refresh_checked\": %llu, \"bpe_refresh_prep_s\": %.4f, \"bpe_refresh_call_s\": %.4f, "
         "\"bpe_refresh_post_s\": %.4f, \"bpe_refresh_erased\": %llu, "
-        "\"read_s\": %.4f, \"trie_build_s\": %.4f, "
+        "\"read_s\": %.4f, \"trie_build_s\": %.4f, \"nbest_host_redo\": %llu, "
         "\"peak_device_bytes\": %llu, \"stage_peak_bytes\": [%llu, %llu, %llu, %llu], "
         "\"seed_stages_ms\": [%.2f, %.2f, %.2f, %.2f, %.2f, %.2f, %.0f]}\n",
         tm.load, tm.seed, tm.seed_device_ms, static_cast<unsigned long long>(tm.seed_candidates),
@@ -157,6 +157,7 @@ int main(int argc, char **argv) {
         static_cast<unsigned long long>(tm.bpe_update_replays), tm.bpe_refresh_device_ms,
         static_cast<unsigned long long>(tm.bpe_refresh_checked), tm.bpe_refresh_prep, tm.bpe_refresh_call,
         tm.bpe_refresh_post, static_cast<unsigned long long>(tm.bpe_refresh_erased), tm.read, tm.trie_build,
+        static_cast<unsigned long long>(tm.nbest_host_redo),
         static_cast<unsigned long long>(tm.peak_device_bytes),
         static_cast<unsigned long long>(tm.stage_peak_bytes[0]), static_cast<unsigned long long>(tm.stage_peak_bytes[1]),
         static_cast<unsigned long long>(tm.stage_peak_bytes[2]), static_cast<unsigned long long>(tm.stage_peak_bytes[3]),

@@ -32,6 +32,7 @@
 
 #include "double_array.h"
 #include "heap_select.h"
+#include "host_prune_nbest.h"
 #include "normalize_device.h"
 #include "normalizer.h"
 #include "scratch_cache.h"
@@ -207,124 +208,6 @@ void PutFloat(int field, float v, std::string *o) {
   std::memcpy(b, &v, 4);
   o->append(b, 4);
 }
-
-// ---- host lattice for NBest(2) of the pruning step -------------------------
-// Lattice (unigram_model.cc:147-261, NBest :339-477) + PopulateNodes
-// (:535-604) with the TrainerModel quirks (unk_id 0, every piece NORMAL).
-struct HostLattice {
-  struct Node {
-    int pos, length, id;
-    float score, bt;
-    int prev;
-  };
-  std::vector<Node> nodes;
-  std::vector<std::vector<int>> begin_nodes, end_nodes;
-  int len = 0;
-
-  void Build(const std::string &s, const DoubleArray &trie, const std::vector<float> &score,
-             float min_score, std::vector<std::pair<int32_t, size_t>> *res) {
-    std::vector<size_t> surface;
-    for (size_t i = 0; i < s.size();) {
-      surface.push_back(i);
-      i += std::min<size_t>(OneCharLen(static_cast<uint8_t>(s[i])), s.size() - i);
-    }
-    surface.push_back(s.size());
-    len = static_cast<int>(surface.size()) - 1;
-    nodes.clear();
-    begin_nodes.assign(len + 1, {});
-    end_nodes.assign(len + 1, {});
-    nodes.push_back({0, 0, -1, 0.f, 0.f, -1});    // BOS
-    nodes.push_back({len, 0, -1, 0.f, 0.f, -1});  // EOS
-    end_nodes[0].push_back(0);
-    begin_nodes[len].push_back(1);
-    const float unk_score = min_score - 10.0f;  // kUnkPenalty
-    for (int b = 0; b < len; ++b) {
-      trie.CommonPrefixSearch(s.data() + surface[b], s.size() - surface[b], res);
-      bool has_single = false;
-      for (auto &r : *res) {
-        const size_t e = surface[b] + r.second;
-        int c = b;
-        while (surface[c] < e) ++c;
-        const int length = c - b;
-        Insert(b, length, r.first, score[r.first]);
-        if (length == 1) has_single = true;
-      }
-      if (!has_single) Insert(b, 1, 0, unk_score);
-    }
-  }
-  void Insert(int pos, int length, int id, float sc) {
-    const int k = static_cast<int>(nodes.size());
-    nodes.push_back({pos, length, id, sc, 0.f, -1});
-    begin_nodes[pos].push_back(k);
-    end_nodes[pos + length].push_back(k);
-  }
-  std::vector<int> Viterbi() {
-    for (int pos = 0; pos <= len; ++pos)
-      for (int r : begin_nodes[pos]) {
-        int best = -1;
-        float best_score = 0.f;
-        for (int l : end_nodes[pos]) {
-          const float sc = nodes[l].bt + nodes[r].score;
-          if (best < 0 || sc > best_score) {
-            best = l;
-            best_score = sc;
-          }
-        }
-        if (best < 0) return {};
-        nodes[r].prev = best;
-        nodes[r].bt = best_score;
-      }
-    std::vector<int> out;
-    for (int k = nodes[begin_nodes[len][0]].prev; nodes[k].prev >= 0; k = nodes[k].prev)
-      out.push_back(k);
-    std::reverse(out.begin(), out.end());
-    return out;
-  }
-  // A* n-best with the same std::priority_queue ordering as the reference.
-  std::vector<std::vector<int>> NBest2() {
-    struct Hyp {
-      int node;
-      Hyp *next;
-      float fx, gx;
-    };
-    struct Cmp {
-      bool operator()(Hyp *a, Hyp *b) const { return a->fx < b->fx; }
-    };
-    using Agenda = std::priority_queue<Hyp *, std::vector<Hyp *>, Cmp>;
-    const size_t nbest_size = 2;
-    std::deque<Hyp> pool;
-    Agenda agenda;
-    std::vector<std::vector<int>> results;
-    const int eos = begin_nodes[len][0], bos = end_nodes[0][0];
-    pool.push_back(Hyp{eos, nullptr, nodes[eos].score, nodes[eos].score});
-    agenda.push(&pool.back());
-    Viterbi();
-    while (!agenda.empty()) {
-      Hyp *top = agenda.top();
-      agenda.pop();
-      if (top->node == bos) {
-        results.emplace_back();
-        for (Hyp *h = top->next; h->next != nullptr; h = h->next) results.back().push_back(h->node);
-        if (results.size() == nbest_size) break;
-        continue;
-      }
-      for (int l : end_nodes[nodes[top->node].pos]) {
-        pool.push_back(Hyp{l, top, nodes[l].bt + top->gx, nodes[l].score + top->gx});
-        agenda.push(&pool.back());
-      }
-      if (agenda.size() >= 100000) {
-        Agenda na;
-        const int size = std::min<int>(512, static_cast<int>(nbest_size * 10));
-        for (int i = 0; i < size; ++i) {
-          na.push(agenda.top());
-          agenda.pop();
-        }
-        agenda = std::move(na);
-      }
-    }
-    return results;
-  }
-};
 
 using Pieces = std::vector<std::pair<std::string, float>>;
 
@@ -2929,6 +2812,7 @@ Status UnigramTrainer::Train(TrainerTimings *tm) {
   t.finalize = Now() - t4;
   t.total = Now() - t0;
   t.trie_build = trie_build_s_;
+  t.nbest_host_redo = nbest_host_redo_;
   stage_peak(3);
   return Status::Ok();
 }

@@ -95,6 +95,9 @@ struct TrainerTimings {
   // (piece sets for the E-steps and pruning: spm_hip_pieces_create,
   // spm_hip_model_from_pieces, the NBest trie).
   double read = 0, trie_build = 0;
+  // Pruning NBest(2) pieces redone on the host (their search outgrew the
+  // device slab of spm_hip_prune_nbest), over all EM rounds.
+  uint64_t nbest_host_redo = 0;
   float seed_stages[7] = {};  // spm_hip_seeds_stage_times
   uint64_t sentences = 0, seed_candidates = 0, em_sentences = 0;
   int em_iterations = 0;

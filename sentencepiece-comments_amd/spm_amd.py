@@ -261,6 +261,22 @@ class DeviceModel:
         _check(fn(b, len(b), ctypes.byref(h)))
         self.h = h
 
+    @classmethod
+    def from_pieces(cls, pieces, scores):
+        """spm_hip_model_from_pieces: the pruning step's Viterbi model over a
+        bare piece list (every piece NORMAL, id = list index, unk id 0)."""
+        self = cls.__new__(cls)
+        self._L = lib()
+        self.h = None
+        buf, off = to_csr([p if isinstance(p, bytes) else p.encode() for p in pieces])
+        sc = np.ascontiguousarray(scores, dtype=np.float32)
+        if len(sc) != len(pieces):
+            raise ValueError("from_pieces needs one score per piece")
+        h = ctypes.c_void_p()
+        _check(self._L.spm_hip_model_from_pieces(_p(buf), _p(off), _p(sc), len(pieces), ctypes.byref(h)))
+        self.h = h
+        return self
+
     def close(self):
         if getattr(self, "h", None):
             self._L.spm_hip_model_free(self.h)
@@ -742,6 +758,7 @@ class DevicePieces:
             raise SpmError(rc, "spm_hip_pieces_create failed")
         self.h = h
         self.V = len(pieces)
+        self._buf, self._off = buf, off
 
     def close(self):
         if getattr(self, "h", None):
@@ -778,6 +795,39 @@ class DevicePieces:
         if len(sc) != self.V:
             raise ValueError("set_scores needs one score per piece")
         self._check(self._L.spm_hip_pieces_set_scores(self.h, _p(sc), self.V))
+
+    def prune_nbest(self):
+        """spm_hip_prune_nbest: NBest(2) of every piece over its own string, as
+        the trainer's pruning step calls it (uses torch for device buffers).
+        Returns (keep uint8[V]: 0 / 1, 2 = the search outgrew the device slab,
+        [the second-best path's ids per piece])."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        buf, off, V = self._buf, self._off, self.V
+        alt_off = np.zeros(V + 1, dtype=np.uint64)  # chars per piece (the longest path)
+        for i in range(V):
+            q, e, n = int(off[i]), int(off[i + 1]), 0
+            while q < e:
+                lead = int(buf[q]) >> 4
+                q += max(1 if lead < 12 else 2 if lead < 14 else lead - 11, 1)
+                n += 1
+            alt_off[i + 1] = alt_off[i] + np.uint64(n)
+        max_bytes = max(int((off[1:] - off[:-1]).max()), 1)
+        d_b = torch.from_numpy(buf).to(dev)
+        d_o = torch.from_numpy(off.view(np.int64)).to(dev)
+        d_ao = torch.from_numpy(alt_off.view(np.int64)).to(dev)
+        d_keep = torch.zeros(V, dtype=torch.uint8, device=dev)
+        d_alt = torch.zeros(max(int(alt_off[V]), 1), dtype=torch.int32, device=dev)
+        d_altn = torch.zeros(V, dtype=torch.int32, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        P = ctypes.c_void_p
+        self._check(self._L.spm_hip_prune_nbest(self.h, P(d_b.data_ptr()), P(d_o.data_ptr()), P(d_keep.data_ptr()),
+                                                P(d_alt.data_ptr()), P(d_ao.data_ptr()), P(d_altn.data_ptr()),
+                                                max_bytes, P(s) if s else None))
+        torch.cuda.synchronize(dev)
+        keep = d_keep.cpu().numpy()
+        alt, alt_n = d_alt.cpu().numpy(), d_altn.cpu().numpy()
+        return keep, [alt[int(alt_off[i]):int(alt_off[i]) + int(alt_n[i])].tolist() for i in range(V)]
 
     def set_forward(self, mode):
         """spm_hip_pieces_set_forward: 0 auto, 1 byte-kernel E-step mode, 2 estep_forward_kernel."""

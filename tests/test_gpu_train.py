@@ -157,13 +157,14 @@ def test_seed_mine_long_max_sentencepiece_length(max_len):
     assert np.array_equal(got_s.view(np.uint32), want_s.view(np.uint32))
 
 
-def _train_gpu(tmp_path, input_path, args, tag, env=None):
+def _train_gpu(tmp_path, input_path, args, tag, env=None, allow_host_redo=False):
     prefix = str(tmp_path / tag)
     cmd = [TRAIN, "--input=" + input_path, "--model_prefix=" + prefix] + args.split()
     p = subprocess.run(cmd, capture_output=True, timeout=600, env=None if env is None else {**os.environ, **env})
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     # pruning NBest(2) ran on the device (spm_hip_prune_nbest) for every piece
-    assert b"outgrew the device slab" not in p.stderr
+    if not allow_host_redo:
+        assert b"outgrew the device slab" not in p.stderr
     em = [l for l in p.stderr.decode().splitlines() if l.startswith("EM sub_iter=")]
     _train_gpu.last_log = p.stderr.decode(errors="replace")
     _train_gpu.last_stdout = p.stdout.decode(errors="replace")
@@ -182,20 +183,60 @@ TRAIN_CASES = [
 ]
 
 
-@pytest.mark.parametrize("corpus,args", TRAIN_CASES)
-def test_spm_train_matches_oracle(corpus, args, tmp_path):
-    path = os.path.join(GOLD, corpus)
-    prefix, em = _train_gpu(tmp_path, path, args, "m")
-    ot = O.OracleTrainer(args, _lines(corpus), _charsmap(_rule_of(args)))
-    wp, ws, wt = ot.train()
+_oracle_cache = {}
+
+
+def _oracle_trained(corpus, args):
+    """(pieces, scores, types, EM log) of the oracle trainer, once per case."""
+    if (corpus, args) not in _oracle_cache:
+        ot = O.OracleTrainer(args, _lines(corpus), _charsmap(_rule_of(args)))
+        wp, ws, wt = ot.train()
+        _oracle_cache[(corpus, args)] = (wp, ws, wt, ot.em_log())
+    return _oracle_cache[(corpus, args)]
+
+
+def _assert_equals_oracle(prefix, em, corpus, args):
+    wp, ws, wt, want_em = _oracle_trained(corpus, args)
     got = model_reader.read_pieces(open(prefix + ".model", "rb").read())
     assert [g[0] for g in got] == wp
     assert np.array_equal(np.array([g[1] for g in got], dtype=np.float32).view(np.uint32),
                           ws.view(np.uint32))
     assert [g[2] for g in got] == list(wt)
     assert open(prefix + ".vocab", "rb").read() == _vocab_text(wp, ws)
-    want_em = ot.em_log()
     assert [l.split(" num_tokens/piece")[0] for l in em] == want_em
+
+
+@pytest.mark.parametrize("corpus,args", TRAIN_CASES)
+def test_spm_train_matches_oracle(corpus, args, tmp_path):
+    path = os.path.join(GOLD, corpus)
+    prefix, em = _train_gpu(tmp_path, path, args, "m")
+    _assert_equals_oracle(prefix, em, corpus, args)
+
+
+@pytest.mark.parametrize("max_hyps", [6, 32])
+def test_spm_train_host_redo_matches_oracle(max_hyps, tmp_path):
+    """The pruning step's host re-run and its glue: with the device search cut
+    to a few hypotheses per piece (SPM_HIP_PRUNE_MAX_HYPS), the pieces it flags
+    are redone by HostLattice::NBest2 and merged back, and the model, the
+    vocab and the EM log still equal the oracle's.
+
+    6 is the hypothesis count of the smallest search with two paths (a
+    two-char piece over its two chars: EOS, two expansions of it, then three
+    more down to the two BOS hypotheses), so every longer search goes to the
+    host and the shortest stay on the device: both sides of the merge hold
+    pieces (15755 host re-runs over the six pruning rounds measured).  At 32
+    no search of this corpus is cut (the largest takes between 17 and 24
+    hypotheses: 0 re-runs at 32, 28 and 24, 87 at 16), so that case only pins
+    the knob's upper side: same model, and the counter and the log agree."""
+    corpus, args = TRAIN_CASES[1]
+    prefix, em = _train_gpu(tmp_path, os.path.join(GOLD, corpus), args + " --timings=true", "redo",
+                            env={"SPM_HIP_PRUNE_MAX_HYPS": str(max_hyps)}, allow_host_redo=True)
+    _assert_equals_oracle(prefix, em, corpus, args)
+    timings = json.loads(_train_gpu.last_stdout.strip().splitlines()[-1])
+    logged = "outgrew the device slab, redone on the host" in _train_gpu.last_log
+    assert (timings["nbest_host_redo"] > 0) == logged
+    if max_hyps == 6:
+        assert logged and timings["nbest_host_redo"] > 0
 
 
 def test_spm_train_known_answer(tmp_path):

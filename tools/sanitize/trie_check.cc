@@ -4,8 +4,10 @@
 // ones placed by one thread, with long shared prefixes, high bytes, NULs,
 // duplicates and empty keys.  Every key is looked up (ExactMatch) and random
 // queries' CommonPrefixSearch results are compared with a std::map of the
-// canonical keys (NUL-truncated, first value of equal keys, empty dropped).
+// canonical keys (NUL-truncated; of keys equal after the truncation the one
+// sorting first as a whole string, equal strings the first; empty dropped).
 // Prints one JSON line; exits 1 on the first mismatch.
+#include <algorithm>
 #include <cstdio>
 #include <map>
 #include <random>
@@ -28,7 +30,10 @@ int Fail(const char *what, const std::string &key) {
 
 int Check(const Keys &keys, std::mt19937 *rng, size_t *queries) {
   std::map<std::string, int32_t> want;
-  for (const auto &k : keys) {
+  Keys sorted = keys;
+  std::stable_sort(sorted.begin(), sorted.end(),
+                   [](const Keys::value_type &a, const Keys::value_type &b) { return a.first < b.first; });
+  for (const auto &k : sorted) {
     std::string s = k.first.substr(0, k.first.find('\0'));
     if (!s.empty()) want.emplace(s, k.second);
   }
@@ -97,7 +102,7 @@ int main() {
     }
     if (run(k)) return 1;
   }
-  // Arbitrary bytes with NULs, duplicates (first value wins) and empty keys.
+  // Arbitrary bytes with NULs, duplicates (of equal strings the first value wins) and empty keys.
   {
     Keys k;
     for (int i = 0; i < 50000; ++i) {
