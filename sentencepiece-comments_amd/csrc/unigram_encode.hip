@@ -39,7 +39,10 @@
 // Output: lanes count their tokens with a first backtrace, the block scans
 // the counts in sentence order and the second backtrace writes ids / piece
 // lengths densely into the tile's slot range (at the tile's first input
-// byte); tile_compact_kernel then places every tile (compact.hip).
+// byte); tile_compact_kernel then places every tile (compact.hip).  The byte
+// encode kernel has no second backtrace: the count leaves the final chain in
+// the back-pointer bytes, the lanes list their tokens as (offset, length)
+// descriptors in LDS and the block looks them up one token per thread.
 //
 // Back-pointers: one byte per char position (end - winner begin), in LDS for
 // byte positions < kLdsBpPos, beyond that in a global scratch array indexed
@@ -144,11 +147,12 @@ void unigram_fast_kernel(FastArgs a) {
   // 10 M c2 sentences (profiles/r03k_root_lds_ab.txt).
   constexpr bool kRootLds = kByte || kWide;
   // Byte encode kernel: the length sort's table, the root table and (once
-  // both are dead) the tile's output ids share one LDS buffer.  The ids are
-  // staged there and written out as one coalesced run per tile: written
+  // both are dead) the output stage's token descriptors share one LDS buffer.
+  // The tile's tokens are staged there, a window of kStageIds at a time, and
+  // looked up and written out one per thread, as coalesced runs: written
   // straight from the backtrace (4 bytes per lane per step, scattered over
-  // the tile's range) they were 640 of the kernel's 750 MB of HBM writes and
-  // cost 420 MB of reads per 10 M sentences (profiles/r04u_pmc_c2_*.json).
+  // the tile's range) the ids were 640 of the kernel's 750 MB of HBM writes
+  // and cost 420 MB of reads per 10 M sentences (profiles/r04u_pmc_c2_*.json).
   // The buffer fills what the 7-block occupancy leaves of the CU's LDS
   // (22.5 KB per block after allocation granularity; at 1472 ids the block
   // rounded past it, 6 blocks fit and the kernel ran 7 % slower).
@@ -394,7 +398,10 @@ void unigram_fast_kernel(FastArgs a) {
     };
     // Offsets past the tile's buffer range (a > 2 GB tile) would read 0:
     // such a sentence takes the general kernel.
-    bad = valid && (b0 - blk_al) + nb > static_cast<uint64_t>(blk_nrec);
+    // The output stage's token descriptors hold a tile-relative offset of 28
+    // bits (kStage): a tile that spans more goes the same way.
+    bad = valid && (b0 - blk_al) + nb >
+                       (kStage && blk_nrec > 0x0FFFFFFF ? 0x0FFFFFFFull : static_cast<uint64_t>(blk_nrec));
     // Window: aligned dwords of the lane's bytes, spliced by alignbyte.
     const uint32_t sh = lrel & 3u;
     const uint32_t lane_al = lrel & ~3u;
@@ -1096,35 +1103,16 @@ void unigram_fast_kernel(FastArgs a) {
   // back-pointer after the forward pass, as a corrupted scratch byte would.
   if (a.corrupt_bp != ~0ull && valid_e && ie == a.corrupt_bp && nb > 0) bp_store(nb, 0);
 
-  // Node (b, e) on the best path: exact-match walk, else UNK.
-  uint32_t wide_node = kNone;  // kWide: the trie unit of the token the backtrace is at
-  auto node_of = [&](uint32_t b, uint32_t e, int32_t *id_out, float *sc_out) {
-    if constexpr (kWide) {
-      // The forward pass kept the winner's unit (kNone: the UNK node).
-      int32_t id = a.p.unk_id;
-      float sc = a.p.unk_score;
-      if (wide_node != kNone) {
-        const int32_t v = a.values[wide_node];
-        const int32_t kind = v >> kKindShift;
-        id = v & kIdMask;
-        if (kind == kKindUserDefined) {
-          int chars = 0;
-          for (uint32_t j = b; j < e; j += OneCharLenDev(byte_at(j))) ++chars;
-          sc = UserDefinedScore(chars, a.p.max_score);
-        } else {
-          sc = a.scores[id];
-        }
-      }
-      *id_out = id;
-      *sc_out = sc;
-      return;
-    }
+  // Byte kernel: the token of `len` bytes at tile-relative offset `ro` (from
+  // blk_al), by its bytes alone: the near-tie resolution of the counting
+  // backtrace and the tile-balanced lookup of the output stage share it.
+  auto token_of = [&](uint32_t ro, uint32_t len, int32_t *id_out, float *sc_out) {
     if constexpr (kByte) {
       // The token's bytes (< 16) from one aligned 16-byte load + one dword
       // instead of a byte gather per byte, walked through (unit, score) pairs:
       // the node score comes with the last unit, so only the id is one more
       // gather (the kernel is bound by its gathers' address work).
-      const uint32_t o = (lrel + b) & ~3u, sh = (lrel + b) & 3u;
+      const uint32_t o = ro & ~3u, sh = ro & 3u;
       uint32_t w[5];
       if (static_cast<uint64_t>(o) + 20 <= blk_rem) {
         const auto x = __builtin_amdgcn_raw_buffer_load_b128(bytes_rsrc, o, 0, 0);
@@ -1154,7 +1142,6 @@ void unigram_fast_kernel(FastArgs a) {
           // zero-padded, the length in the last byte; the table holds exactly
           // the usable trie nodes, so a miss is what the walk calls UNK (an
           // inner or UNUSED node, no node, a NUL inside the token).
-          const uint32_t len = e - b;
           const int n = static_cast<int>(len);
           auto keep = [](uint32_t r, int nb) { return nb >= 4 ? r : nb <= 0 ? 0u : r & ~(~0u << (8 * nb)); };
           const uint32_t k0 = keep(r0, n), k1 = keep(r1, n - 4), k2 = keep(r2, n - 8);
@@ -1193,7 +1180,7 @@ void unigram_fast_kernel(FastArgs a) {
                                                               static_cast<int>(a.num_units * 8u), 0x00020000);
       uint32_t nbase = a.p.root_base, node = 0, u = 0, scb = 0;
       bool found = true;
-      for (uint32_t j = b; j < e; ++j) {
+      for (uint32_t j = 0; j < len; ++j) {
         const uint32_t c = r0 & 0xFFu;
         r0 = __builtin_amdgcn_alignbyte(r1, r0, 1);
         r1 = __builtin_amdgcn_alignbyte(r2, r1, 1);
@@ -1216,13 +1203,40 @@ void unigram_fast_kernel(FastArgs a) {
       // A usable node (leaf, not UNUSED) is exactly one with a non-NaN score
       // in the pair table (the byte kernel's models have no NaN score).
       const float s_node = __uint_as_float(scb);
-      if (found && b < e && !__builtin_isnan(s_node)) {
+      if (found && len > 0 && !__builtin_isnan(s_node)) {
         *id_out = a.values[node] & kIdMask;
         *sc_out = s_node;
       } else {
         *id_out = a.p.unk_id;
         *sc_out = a.p.unk_score;
       }
+    }
+  };
+  // Node (b, e) on the best path: exact-match walk, else UNK.
+  uint32_t wide_node = kNone;  // kWide: the trie unit of the token the backtrace is at
+  auto node_of = [&](uint32_t b, uint32_t e, int32_t *id_out, float *sc_out) {
+    if constexpr (kWide) {
+      // The forward pass kept the winner's unit (kNone: the UNK node).
+      int32_t id = a.p.unk_id;
+      float sc = a.p.unk_score;
+      if (wide_node != kNone) {
+        const int32_t v = a.values[wide_node];
+        const int32_t kind = v >> kKindShift;
+        id = v & kIdMask;
+        if (kind == kKindUserDefined) {
+          int chars = 0;
+          for (uint32_t j = b; j < e; j += OneCharLenDev(byte_at(j))) ++chars;
+          sc = UserDefinedScore(chars, a.p.max_score);
+        } else {
+          sc = a.scores[id];
+        }
+      }
+      *id_out = id;
+      *sc_out = sc;
+      return;
+    }
+    if constexpr (kByte) {
+      token_of(lrel + b, e - b, id_out, sc_out);
       return;
     }
     uint32_t nbase = a.p.root_base, node = 0, u = 0;
@@ -1256,39 +1270,41 @@ void unigram_fast_kernel(FastArgs a) {
     *id_out = id;
     *sc_out = sc;
   };
-  uint32_t stage_base = 0;  // kStage: the lane's first tile-local token index
   // Backtrace from EOS (score 0).  write=false only counts tokens (node
   // scores are needed only to resolve recorded near-ties).  Every step must
   // move left (begin < end): a zero or out-of-range back-pointer flags the
-  // sentence instead of looping.
+  // sentence instead of looping.  (kStage runs only the counting form.)
   auto backtrace = [&](bool write, int32_t *out_id, uint32_t *out_len, uint32_t kt) -> uint32_t {
     uint32_t e = nb, k = 0;
     float rs = 0.f;
     while (e > 0) {
       uint32_t b = e - bp_load(e);
       if constexpr (kWide) wide_node = (write || any_amb) ? a.bpn[b0 + e] : kNone;
+      bool second = false;
 #pragma unroll
       for (int t = 0; t < kAmb; ++t)
         if (ae[t] == e && __fadd_rn(aT2[t], rs) == __fadd_rn(aT[t], rs)) {
           b = aB2[t];
+          second = true;
           if constexpr (kWide) wide_node = aN2[t];
         }
-      if (b >= e || k >= nb) {
+      // kStage: a token is also at most 15 bytes (its length is a descriptor's
+      // 4 bits); b >= e wraps e - b - 1 past that.
+      if ((kStage ? e - b - 1u >= 15u : b >= e) || k >= nb) {
         bad = true;
         return 0;
       }
+      // kStage: the second setter won.  Its distance replaces the first
+      // setter's in the back-pointer byte, so the chain this (counting) pass
+      // leaves there is the final path and the describe pass follows it blind.
+      if constexpr (kStage)
+        if (second) bp_store(e, e - b);
       if (write || any_amb) {
         int32_t id;
         float sc;
         node_of(b, e, &id, &sc);
         if (write) {
-          if constexpr (kStage) {
-            const uint32_t li = stage_base + (kt - 1 - k);  // tile-local token index
-            if (li < kStageIds) lds_stage[li] = id;
-            else out_id[kt - 1 - k] = id;
-          } else {
-            out_id[kt - 1 - k] = id;
-          }
+          out_id[kt - 1 - k] = id;
           if (out_len) out_len[kt - 1 - k] = e - b;
         }
         rs = sc;
@@ -1354,19 +1370,51 @@ void unigram_fast_kernel(FastArgs a) {
       atomicMax(&a.status[kStMaxNb], nb);
       a.tok_off[ie + 1] = rec | kTokFlag;
     } else {
-      stage_base = static_cast<uint32_t>(rec);
-      if (k) backtrace(true, out_ids + dst, out_len ? out_len + dst : nullptr, k);
+      if constexpr (!kStage)
+        if (k) backtrace(true, out_ids + dst, out_len ? out_len + dst : nullptr, k);
       a.tok_off[ie + 1] = rec + k;
     }
   }
   if (tile == 0 && tid == 0) a.tok_off[0] = 0;
   if constexpr (kStage) {
-    // The staged ids (the tile's first kStageIds tokens) as one coalesced run.
-    __syncthreads();
-    const uint32_t tot = lds_wave[0] + lds_wave[1] + lds_wave[2] + lds_wave[3];
-    const uint32_t m = tot < kStageIds ? tot : kStageIds;
-    int32_t *__restrict__ dst0 = out_ids + a.off[base];
-    for (uint32_t t = static_cast<uint32_t>(tid); t < m; t += kBlock) dst0[t] = static_cast<int32_t>(lds_stage[t]);
+    // The tile's tokens in windows of kStageIds tile-local indices, the last
+    // window first (lanes walk their chain from the end).  Per window the
+    // lanes describe their tokens in it — (tile-relative byte offset) << 4 |
+    // length, following the back-pointer bytes and nothing else: the counting
+    // pass validated the chain and resolved its near ties — and then the
+    // block looks the window's tokens up one per thread, all lanes busy and
+    // consecutive lanes storing consecutive words.  (Looked up in the lane's
+    // own backtrace a token cost its ~120 vector instructions once per
+    // lockstep round, the wave's longest lane many rounds: 11.2 rounds for
+    // 4.3 tokens per lane on the c2 corpus, tools/backtrace_model.py.)
+    // Every thread runs every window and both of its barriers; a flagged,
+    // invalid or empty lane holds no tokens (k == 0).
+    const uint32_t tot =
+        __builtin_amdgcn_readfirstlane(lds_wave[0] + lds_wave[1] + lds_wave[2] + lds_wave[3]);  // block-uniform
+    const uint32_t rec32 = static_cast<uint32_t>(rec);
+    int32_t *__restrict__ dst_ids = out_ids + a.off[base];
+    uint32_t *__restrict__ dst_len = out_len ? out_len + a.off[base] : nullptr;
+    uint32_t e = nb, j = k;  // the lane's tokens [rec32, rec32 + j) are yet to be described, ending at byte e
+    for (uint32_t w = (tot + kStageIds - 1u) / kStageIds; w-- > 0;) {
+      const uint32_t lo = w * kStageIds;
+      while (j > 0 && rec32 + j > lo) {
+        const uint32_t d = bp_load(e);
+        e -= d;
+        --j;
+        lds_stage[rec32 + j - lo] = ((lrel + e) << 4) | d;
+      }
+      __syncthreads();
+      const uint32_t m = tot - lo < kStageIds ? tot - lo : kStageIds;
+      for (uint32_t t = static_cast<uint32_t>(tid); t < m; t += kBlock) {
+        const uint32_t desc = lds_stage[t];
+        int32_t id;
+        float sc;
+        token_of(desc >> 4, desc & 15u, &id, &sc);
+        dst_ids[lo + t] = id;
+        if (dst_len) dst_len[lo + t] = desc & 15u;
+      }
+      if (w) __syncthreads();  // the next window overwrites the stage (w is block-uniform)
+    }
   }
   if (a.host_pub) {
     // Single-tile host call: every wave's output stores (pinned host memory)
