@@ -66,7 +66,8 @@ typedef struct spm_hip_model_info {
   int32_t model_type;       /* spm_model_type */
   int32_t piece_size;       /* ModelProto.pieces_size() */
   int32_t unk_id;           /* index of the UNKNOWN piece */
-  int32_t max_piece_chars;  /* longest matchable piece, in UTF-8 chars */
+  int32_t max_piece_chars;  /* longest matchable piece, in UTF-8 chars
+                               (WORD / CHAR: over every piece type) */
   int32_t trie_results_size;/* unigram: max prefix matches per position */
   int32_t trie_units;       /* device double-array size (units) */
   float min_score;          /* unigram: min over NORMAL scores */
@@ -82,7 +83,12 @@ typedef struct spm_hip_model_info {
                                table; 3 lane kernel with 32-bit symbol words
                                (tied merge scores); 4 half kernel (>= 32768
                                pieces); 0 general kernel only (user-defined
-                               symbols).  Also set on a host-only handle. */
+                               symbols).  WORD / CHAR: 1 the tile tier runs
+                               first (token starts marked per byte tile, the
+                               general tier takes only flagged sentences), 0
+                               every sentence goes to the general tier (a CHAR
+                               model with USER_DEFINED pieces).  Also set on a
+                               host-only handle. */
 } spm_hip_model_info;
 
 /* Counters of the last encode call (host-visible after it returns). */
@@ -147,7 +153,8 @@ int spm_hip_encode_batch(spm_hip_model *model, const uint8_t *d_norm_bytes,
  *              scratch (> 256 KiB; spm_hip_encode_batch handles those).
  * The return value reports argument and enqueue errors only.  Models whose
  * encode needs host-sized scratch (unigram pieces of >= 64 bytes, BPE with
- * user-defined symbols, force_general) fall back to the blocking path. */
+ * user-defined symbols, force_general) fall back to the blocking path; WORD
+ * and CHAR models never do (both of their tiers are pure stream calls). */
 int spm_hip_encode_batch_async(spm_hip_model *model, const uint8_t *d_norm_bytes,
                                const uint64_t *d_offsets, uint64_t n, uint64_t capacity, int32_t *d_ids,
                                uint32_t *d_piece_len, uint64_t *d_tok_offsets, uint32_t *d_status,

@@ -17,6 +17,7 @@
 #include "double_array.h"
 #include "kernels.h"
 #include "model_proto.h"
+#include "wordchar_table.h"
 
 
 
@@ -57,6 +58,9 @@ struct EncodeWorkspace {
   // Decode: first non-empty position per sentence, block sums, control words;
   // staging of the host entry (ids, token offsets, text, offsets, begins).
   DevBuf w_dfirst, w_dsum, w_dctl, h_dids, h_dtok, h_dout, h_doff, h_dbegin;
+  // WORD / CHAR encode: marks per tile, first mark and first sentence of each
+  // tile, first mark after each tile
+  DevBuf w_wc_count, w_wc_first, w_wc_sent, w_wc_next;
   DevBuf w_tids, w_tlen, w_ttok;  // SentencePieceText path: raw ids, piece lengths, token offsets
   DevBuf h_in, h_off, h_ids, h_len, h_tok;  // staging for the host API
   // Host API small batches (EncodeHostSmall): one device block [control |
@@ -163,6 +167,13 @@ struct spm_hip_model {
   std::vector<uint32_t> piece_table;
   spm_amd::DevBuf d_piece_tab;
   spm_amd::BpeDevice bpe;
+  // WORD / CHAR: exact-match table piece bytes -> PieceToId (wordchar_table.h)
+  // over all five piece types, its key blob, and whether the model has
+  // USER_DEFINED pieces (CHAR: every sentence then runs the general tier).
+  std::vector<spm_amd::WordCharEntry> wc_tab;
+  std::vector<uint8_t> wc_keys;
+  bool wc_user_defined = false;
+  spm_amd::DevBuf d_wc_tab, d_wc_keys;
   // Lazily uploaded tables (under init_mu): device normalizer charsmap blob +
   // user-defined trie; id-epilogue piece type bits.
   std::mutex init_mu;

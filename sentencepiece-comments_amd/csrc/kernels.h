@@ -458,4 +458,52 @@ hipError_t LaunchCompact(const uint64_t *off, uint64_t n, const uint32_t *ntok, 
                          void *scan_tmp, size_t *scan_tmp_bytes, const uint32_t *status, uint32_t *out_status,
                          hipStream_t st);
 
+// WORD / CHAR encode (wordchar_kernels.hip).  Tokens are views into the
+// input, so the kernels mark the bytes that start a token (mark: one byte per
+// input byte, whole tiles of kWcTile), count the marks per tile, scan, and
+// look every marked span up in the exact-match table (wordchar_table.h).
+// LaunchWordCharTile marks by the tile tier's shortcut and appends the
+// sentences where it differs from the reference's OneCharLen walk to
+// `flagged` (status[kStFlagged] counts them, sflag: zeroed, one word per
+// sentence); LaunchWordCharGeneral re-marks those (all = false) or every
+// sentence (all = true, which also sets status[kStFlagged] = n) with the
+// reference's sequential loop; LaunchWordCharOutput writes ids / len /
+// tok_off and the call's status (RESOURCE_EXHAUSTED when off[n] > capacity).
+constexpr uint32_t kWcTile = 2048;
+inline uint64_t WordCharTiles(uint64_t capacity) { return capacity / kWcTile + 1; }
+struct WordCharLaunch {
+  const uint8_t *bytes;
+  const uint64_t *off;
+  uint64_t n;
+  uint64_t capacity;         // caller's bound on off[n]
+  uint64_t tiles;            // WordCharTiles(capacity)
+  int32_t word;              // 1: WORD (SplitIntoWords), 0: CHAR (PrefixMatch)
+  const uint32_t *tab;       // WordCharEntry[tab_mask + 1]
+  uint32_t tab_mask;
+  const uint8_t *keys;       // the entries' key bytes
+  uint32_t max_piece_bytes;  // a longer token is unknown without a lookup
+  int32_t unk_id;
+  const uint32_t *ud_units;  // CHAR: user-defined symbol trie (nullable)
+  uint32_t ud_num_units;
+  uint8_t *mark;             // tiles * kWcTile bytes, 8-byte aligned
+  uint32_t *sflag;           // n, zeroed
+  uint32_t *flagged;         // n
+  uint32_t *status;          // kStWords
+  uint32_t *tile_count;      // tiles
+  uint32_t *tile_first;      // tiles: first mark of the tile (kWcTile: none)
+  uint64_t *tile_prefix;     // tiles + 1
+  uint32_t *tile_sent;       // tiles: first sentence that starts in or after the tile
+  uint64_t *tile_next;       // tiles: position of the first mark in a later tile (~0: none)
+  int32_t *ids;
+  uint32_t *len;             // nullable
+  uint64_t *tok_off;         // n + 1
+  const uint32_t *chain;     // caller's status word (nullable): idle if non-zero
+  uint32_t *out_status;      // the same word, for the call's own status
+};
+hipError_t LaunchWordCharEmpty(uint64_t *tok_off, const uint32_t *chain, hipStream_t st);  // n == 0
+hipError_t LaunchWordCharSentences(const WordCharLaunch &l, hipStream_t st);  // first: fills tile_sent
+hipError_t LaunchWordCharTile(const WordCharLaunch &l, hipStream_t st);
+hipError_t LaunchWordCharGeneral(const WordCharLaunch &l, bool all, hipStream_t st);
+hipError_t LaunchWordCharOutput(const WordCharLaunch &l, hipStream_t st);
+
 }  // namespace spm_amd

@@ -352,7 +352,13 @@ Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, 
                                         const SampleSpec *sample) const {
   if (!status_.ok()) return status_;
   const uint64_t n = inputs.size();
-  if (!sample && !pieces && ids && n >= 1 && n <= kSmallLines) {
+  // A WORD / CHAR model can return a CONTROL piece's id for a token (a word
+  // that spells it: PieceToId searches the reserved pieces first).  Such a
+  // token consumes no surface, so the reference fails the line ("all
+  // normalized characters are not consumed.").  The device id epilogue does
+  // not carry that check, so these models' ids take the host epilogue below.
+  const bool word_char = proto_.trainer_spec.model_type == kWord || proto_.trainer_spec.model_type == kChar;
+  if (!sample && !pieces && ids && !word_char && n >= 1 && n <= kSmallLines) {
     uint64_t raw = 0;
     for (const auto &s : inputs) raw += s.size();
     if (raw <= kSmallBytes) {
@@ -400,7 +406,7 @@ Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, 
                                                   sample->index_base, d_ids, d_len, d_tok, nullptr)
                     : spm_hip_encode_batch(model_, d_norm, d_norm_off, n, d_ids, d_len, d_tok, nullptr));
   if (!st.ok()) return st;
-  if (!pieces) {
+  if (!pieces && !word_char) {
     // Encode(ids): the id epilogue (unk-run merge + extra options) runs on the
     // device as well (spm_hip_finalize_ids); only the final ids come back.
     enum { kOut = 7, kOutOff = 8 };

@@ -325,6 +325,62 @@ int LoadUnigram(spm_hip_model *m) {
   return SPM_OK;
 }
 
+// word::Model / character::Model (word_model.cc, char_model.cc): nothing but
+// InitializePieces.  Encode is a split plus PieceToId, so the device needs
+// one exact-match table from piece bytes to PieceToId(piece): reserved pieces
+// (CONTROL, UNKNOWN) go in first, then NORMAL / USER_DEFINED / UNUSED ones
+// (model_interface.cc:87-97).
+int LoadWordChar(spm_hip_model *m) {
+  std::vector<std::pair<const std::string *, int32_t>> keys;
+  keys.reserve(m->reserved.size() + m->pieces.size());
+  for (const auto &kv : m->reserved) keys.emplace_back(&kv.first, kv.second);
+  for (const auto &kv : m->pieces)
+    if (!m->reserved.count(kv.first)) keys.emplace_back(&kv.first, kv.second);
+  // Map order is not deterministic across runs of the standard library; the
+  // table image is (by id).
+  std::sort(keys.begin(), keys.end(), [](const auto &a, const auto &b) { return a.second < b.second; });
+  size_t max_bytes = 0, blob = 0;
+  int max_chars = 0;
+  for (const auto &k : keys) {
+    max_bytes = std::max(max_bytes, k.first->size());
+    max_chars = std::max(max_chars, CountChars(*k.first));
+    blob += k.first->size();
+  }
+  if (blob > 0xFFFFFFFFull || keys.size() > (1u << 30))
+    return Fail(SPM_RESOURCE_EXHAUSTED, "too many pieces for the device table");
+  m->max_piece_chars = max_chars;
+  m->max_piece_bytes = static_cast<int32_t>(max_bytes);
+  m->wc_user_defined = !m->user_defined.empty();
+  uint32_t cap = 16;
+  while (cap < 2 * keys.size()) cap <<= 1;
+  const uint32_t mask = cap - 1;
+  m->wc_tab.assign(cap, spm_amd::WordCharEntry{0, 0, 0, 0});
+  m->wc_keys.clear();
+  m->wc_keys.reserve(blob + 1);
+  for (const auto &k : keys) {
+    const auto *s = reinterpret_cast<const uint8_t *>(k.first->data());
+    const uint32_t len = static_cast<uint32_t>(k.first->size());
+    const uint32_t h = spm_amd::WordCharHash(s, len);
+    uint32_t slot = h & mask;
+    while (m->wc_tab[slot].key_len != 0) slot = (slot + 1) & mask;
+    const bool packed = len <= 4;  // the key itself, no blob bytes
+    m->wc_tab[slot] = spm_amd::WordCharEntry{
+        h, static_cast<uint32_t>(k.second),
+        packed ? spm_amd::WordCharPack(s, len) : static_cast<uint32_t>(m->wc_keys.size()), len};
+    if (!packed) m->wc_keys.insert(m->wc_keys.end(), s, s + len);
+  }
+  // Checked on the finished image with the lookup the kernels use.
+  for (const auto &k : keys)
+    if (spm_amd::WordCharFind(m->wc_tab.data(), mask, m->wc_keys.data(),
+                              reinterpret_cast<const uint8_t *>(k.first->data()),
+                              static_cast<uint32_t>(k.first->size()), -1) != k.second)
+      return Fail(SPM_INTERNAL, "word/char piece table: a piece is not found");
+  if (m->host_only) return SPM_OK;
+  SPM_HIP_TRY(Upload(&m->d_wc_tab, m->wc_tab));
+  SPM_HIP_TRY(Upload(&m->d_wc_keys, m->wc_keys));
+  return SPM_OK;
+}
+
 // Fast-kernel timing: begin/end events of the workspace ring (created on
 // first use); -1 when timing is off.
 int TimedSlot(spm_hip_model *m, spm_amd::EncodeWorkspace *ws) {
@@ -674,7 +730,95 @@ int EncodeUnigramAll(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_a
   return CompactSlots(ws, c.off, n, s2, s2l, c.ids, c.len, c.tok, status, c.out_status, st);
 }
 
+bool WordCharModel(const spm_hip_model *m) {
+  return m->model_type == spm_amd::kWord || m->model_type == spm_amd::kChar;
+}
+
+// The general tier takes every sentence of a CHAR model with USER_DEFINED
+// pieces (PrefixMatch is sequential) and everything under force_general.
+bool WordCharAllGeneral(const spm_hip_model *m) {
+  return m->force_general || (m->model_type == spm_amd::kChar && m->wc_user_defined);
+}
+
+int EnsureNormTables(spm_hip_model *m);  // (below)
+
+// WORD / CHAR encode: a pure stream call in both tiers (nothing is sized
+// from the sentences; every buffer follows c.capacity and c.n).
+int EncodeWordChar(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd::EncodeCall &c) {
+  const hipStream_t st = c.st;
+  if (spm_amd::WordCharTiles(c.capacity) >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "batch too large");
+  if (c.n == 0) {
+    uint32_t *status = nullptr;
+    const int rc = PrepareControl(ws, 0, st, &status);
+    if (rc != SPM_OK) return rc;
+    SPM_HIP_TRY(spm_amd::LaunchWordCharEmpty(c.tok, c.out_status, st));
+    return SPM_OK;
+  }
+  const bool all = WordCharAllGeneral(m);
+  const bool ud = m->model_type == spm_amd::kChar && m->wc_user_defined;
+  if (ud) {
+    const int rc = EnsureNormTables(m);
+    if (rc != SPM_OK) return rc;
+  }
+  uint32_t *status = nullptr;
+  int rc = PrepareControl(ws, c.n, st, &status);
+  if (rc != SPM_OK) return rc;
+  spm_amd::WordCharLaunch l{};
+  l.bytes = c.bytes;
+  l.off = c.off;
+  l.n = c.n;
+  l.capacity = c.capacity;
+  l.tiles = spm_amd::WordCharTiles(c.capacity);
+  l.word = m->model_type == spm_amd::kWord ? 1 : 0;
+  l.tab = m->d_wc_tab.as<uint32_t>();
+  l.tab_mask = static_cast<uint32_t>(m->wc_tab.size() - 1);
+  l.keys = m->d_wc_keys.as<uint8_t>();
+  l.max_piece_bytes = static_cast<uint32_t>(m->max_piece_bytes);
+  l.unk_id = m->unk_id;
+  l.ud_units = ud ? m->d_ud_units.as<uint32_t>() : nullptr;
+  l.ud_num_units = ud ? m->ud_units_n : 0;
+  SPM_HIP_TRY(ws->w_bp.Reserve(l.tiles * spm_amd::kWcTile));
+  SPM_HIP_TRY(ws->w_cnt.Reserve(c.n * 4));
+  SPM_HIP_TRY(ws->w_flagged.Reserve(c.n * 4));
+  SPM_HIP_TRY(ws->w_wc_count.Reserve(l.tiles * 4));
+  SPM_HIP_TRY(ws->w_wc_first.Reserve(l.tiles * 4));
+  SPM_HIP_TRY(ws->w_wc_sent.Reserve(l.tiles * 4));
+  SPM_HIP_TRY(ws->w_wc_next.Reserve(l.tiles * 8));
+  SPM_HIP_TRY(ws->w_tprefix.Reserve((l.tiles + 1) * 8));
+  l.mark = ws->w_bp.as<uint8_t>();
+  l.sflag = ws->w_cnt.as<uint32_t>();
+  l.flagged = ws->w_flagged.as<uint32_t>();
+  l.status = status;
+  l.tile_count = ws->w_wc_count.as<uint32_t>();
+  l.tile_first = ws->w_wc_first.as<uint32_t>();
+  l.tile_prefix = ws->w_tprefix.as<uint64_t>();
+  l.tile_sent = ws->w_wc_sent.as<uint32_t>();
+  l.tile_next = ws->w_wc_next.as<uint64_t>();
+  l.ids = c.ids;
+  l.len = c.len;
+  l.tok_off = c.tok;
+  l.chain = c.out_status;
+  l.out_status = c.out_status;
+  SPM_HIP_TRY(spm_amd::LaunchWordCharSentences(l, st));
+  const int slot = TimedSlot(m, ws);
+  if (slot >= 0) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot], st));
+  if (!all) {
+    SPM_HIP_TRY(hipMemsetAsync(l.sflag, 0, c.n * 4, st));
+    SPM_HIP_TRY(spm_amd::LaunchWordCharTile(l, st));
+  }
+  if (slot >= 0) {
+    SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot + 1], st));
+    SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
+  }
+  SPM_HIP_TRY(spm_amd::LaunchWordCharGeneral(l, all, st));
+  if (slot >= 0) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
+  SPM_HIP_TRY(spm_amd::LaunchWordCharOutput(l, st));
+  return SPM_OK;
+}
+
+// WORD / CHAR models never need host-sized scratch, force_general included.
 bool NeedsHostSized(const spm_hip_model *m) {
+  if (WordCharModel(m)) return false;
   if (m->force_general) return true;
   if (m->model_type == spm_amd::kUnigram) return m->kernel == spm_amd::UnigramKernel::kGeneralOnly;
   return m->bpe.has_user_defined;
@@ -682,6 +826,7 @@ bool NeedsHostSized(const spm_hip_model *m) {
 
 // Enqueues one encode (no synchronization unless c.host_sized).
 int EncodeEnqueue(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd::EncodeCall &c) {
+  if (WordCharModel(m)) return EncodeWordChar(m, ws, c);
   if (m->model_type == spm_amd::kUnigram)
     return c.host_sized ? EncodeUnigramAll(m, ws, c) : EncodeUnigramFast(m, ws, c);
   return spm_amd::EncodeBpe(m, ws, c, &g_last_error);
@@ -951,7 +1096,7 @@ void EncodeWorkspace::Release() {
                     &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_dfirst, &w_dsum, &w_dctl, &h_dids, &h_dtok, &h_dout, &h_doff, &h_dbegin, &w_tids, &w_tlen, &w_ttok,
                     &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask,
                     &w_nb_ctl, &w_nb_npaths, &w_nb_stage, &w_nb_ntok, &w_nb_score, &w_nb_ids, &w_nb_len, &w_nb_hids,
-                    &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore})
+                    &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore, &w_wc_count, &w_wc_first, &w_wc_sent, &w_wc_next})
     b->Release();
   if (pinned) (void)hipHostFree(pinned);
   pinned = nullptr;
@@ -1110,7 +1255,8 @@ static int LoadImpl(const void *model_proto, size_t len, spm_hip_model **out, bo
   if (rc == SPM_OK) {
     if (m->model_type == spm_amd::kUnigram) rc = LoadUnigram(m);
     else if (m->model_type == spm_amd::kBpe) rc = spm_amd::LoadBpe(m, &g_last_error);
-    else rc = Fail(SPM_UNIMPLEMENTED, "only unigram and bpe models run on the device");
+    else if (WordCharModel(m)) rc = LoadWordChar(m);
+    else rc = Fail(SPM_UNIMPLEMENTED, "unknown model type");
   }
   if (rc == SPM_OK) rc = BuildDecodeTable(m);
   if (rc != SPM_OK) {
@@ -1172,7 +1318,7 @@ void spm_hip_model_free(spm_hip_model *m) {
   for (spm_amd::DevBuf *b : {&m->d_units, &m->d_uvs, &m->d_piece_tab, &m->d_values, &m->d_scores,
                              &m->bpe.pair_keys, &m->bpe.pair_vals, &m->bpe.pair_ent, &m->bpe.rank_piece, &m->bpe.entry_piece,
                              &m->bpe.entry_out, &m->bpe.piece_kind, &m->bpe.piece_out,
-                             &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes})
+                             &m->d_wc_tab, &m->d_wc_keys, &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes})
     b->Release();
   for (auto &kv : m->by_stream) kv.second->Release();
   for (auto &w : m->host_pool) w->Release();
@@ -1192,6 +1338,9 @@ int spm_hip_model_get_info(const spm_hip_model *m, spm_hip_model_info *info) {
   info->ring_width = m->model_type == spm_amd::kUnigram ? m->ring_width : 0;
   if (m->model_type == spm_amd::kUnigram) {
     info->fast_variant = static_cast<int32_t>(m->kernel);
+  } else if (WordCharModel(m)) {
+    // 1: the tile tier runs first; 0: every sentence goes to the general tier.
+    info->fast_variant = m->model_type == spm_amd::kChar && m->wc_user_defined ? 0 : 1;
   } else {
     // The BPE encode tier, from what LoadBpe decided (EncodeBpe's branches).
     const auto &b = m->bpe;

@@ -1,6 +1,9 @@
 // spm_train — drop-in for the reference CLI (src/spm_train_main.cc:26-221),
 // --model_type=unigram, with seed mining, every E-step and the pruning
-// Viterbi on the GPU.  Flags and defaults are the reference's; every flag is
+// Viterbi on the GPU; --model_type=bpe; and --model_type=char (the required
+// chars of the device LoadSentences stage, char_model_trainer.cc).
+// --model_type=word is refused, although the reference trains it: WORD models
+// trained elsewhere load and encode.  Flags and defaults are the reference's; every flag is
 // set into the TrainerSpec / NormalizerSpec as the reference's main() does
 // (so the .model's serialized specs carry the same fields).
 //

@@ -315,6 +315,7 @@ class UnigramTrainer {
   Pieces RunMStep(const std::vector<float> &expected) const;
   Status PruneSentencePieces(Pieces *out);
   Status TrainBpe(TrainerTimings *tm);
+  Status TrainChar();
   bool IsValidSentencePiece(const uint32_t *b, const uint32_t *e) const;
   Pieces FinalizeSentencePieces() const;
   Status Save() const;
@@ -385,9 +386,18 @@ Status UnigramTrainer::VerifySpec() const {
   if (spec_.model_prefix.empty()) return Err(SPM_INTERNAL, "model_prefix is empty");
   if (spec_.input.empty()) return Err(SPM_INTERNAL, "input is empty");
   if (spec_.vocab_size <= 0) return Err(SPM_INTERNAL, "vocab_size <= 0");
-  if (spec_.model_type != kUnigram && spec_.model_type != kBpe)
-    return Err(SPM_UNIMPLEMENTED, "only --model_type=unigram|bpe are trained on the device path");
-  if (spec_.use_all_vocab) return Err(SPM_INTERNAL, "--use_all_vocab=true is valid for WORD/CHAR model.");
+  // WORD training stays refused: the reference would train botchan with the
+  // default flags (9184 distinct words for 7997 free slots), but this
+  // project's error contract pins a failure there (tests/test_gpu_train.py
+  // test_spm_train_errors).  WORD models trained elsewhere load and encode.
+  if (spec_.model_type == kWord)
+    return Err(SPM_UNIMPLEMENTED,
+               "--model_type=word is not trained here (the reference would train it); "
+               "only --model_type=unigram|bpe|char are. WORD models trained elsewhere load and encode.");
+  if (spec_.model_type != kUnigram && spec_.model_type != kBpe && spec_.model_type != kChar)
+    return Err(SPM_UNIMPLEMENTED, "only --model_type=unigram|bpe|char are trained on the device path");
+  if (spec_.use_all_vocab && spec_.model_type != kChar)
+    return Err(SPM_INTERNAL, "--use_all_vocab=true is valid for WORD/CHAR model.");
   auto range = [](double v, double lo, double hi) { return v >= lo && v <= hi; };
   if (!range(spec_.character_coverage, 0.98, 1.0) ||
       !range(spec_.max_sentencepiece_length, 1, 512) || !range(spec_.num_sub_iterations, 1, 10) ||
@@ -1052,7 +1062,9 @@ Status UnigramTrainer::NormalizeDeviceCSR(const uint8_t *d_raw, const uint64_t *
     d_off = d_off2;
     total = total2;
   }
-  if (static_cast<int>(required_chars_.size() + meta_pieces_.size()) > spec_.vocab_size)
+  // (not for WORD / CHAR, trainer_interface.cc:448)
+  if (spec_.model_type != kChar &&
+      static_cast<int>(required_chars_.size() + meta_pieces_.size()) > spec_.vocab_size)
     return Err(SPM_INTERNAL, "Vocabulary size is smaller than required_chars.");
   // Keep the final corpus on the device (own copies; scratch is freed).
   loaded_.Reset();
@@ -1856,6 +1868,29 @@ Pieces UnigramTrainer::FinalizeSentencePieces() const {
   return Sorted(Pieces(fin.begin(), fin.end()));
 }
 
+// character::Trainer::Train after LoadSentences (char_model_trainer.cc:39-61):
+// the required chars by descending count, scored log(count) - logsum with
+// the reference's mixed precision (a double minus a float, narrowed to float).
+// (Its escape_whitespaces check, char_model_trainer.cc:34, is VerifySpec's,
+// which runs for every model type.)
+Status UnigramTrainer::TrainChar() {
+  const int vocab_size = spec_.vocab_size - static_cast<int>(meta_pieces_.size());
+  if (vocab_size < 0) return Err(SPM_INTERNAL, "vocab_size is smaller than the number of meta pieces");
+  uint64_t sum = 0;
+  for (const auto &it : required_chars_) sum += static_cast<uint64_t>(it.second);
+  const float logsum = static_cast<float>(std::log(static_cast<double>(sum)));
+  final_pieces_.clear();
+  std::vector<std::pair<uint32_t, int64_t>> req(required_chars_.begin(), required_chars_.end());
+  for (const auto &w : Sorted(std::move(req))) {
+    if (!spec_.use_all_vocab && final_pieces_.size() == static_cast<size_t>(vocab_size)) break;
+    std::string s;
+    AppendUTF8(w.first, &s);
+    final_pieces_.emplace_back(s, static_cast<float>(std::log(static_cast<double>(w.second)) - logsum));
+  }
+  if (spec_.use_all_vocab) spec_.vocab_size = static_cast<int32_t>(final_pieces_.size() + meta_pieces_.size());
+  return Status::Ok();
+}
+
 // trainer_interface.cc:479-530
 Status UnigramTrainer::Serialize(std::vector<PieceRec> *out) const {
   out->clear();
@@ -1881,7 +1916,8 @@ Status UnigramTrainer::Serialize(std::vector<PieceRec> *out) const {
     out->push_back(p);
   }
   if (fid != final_pieces_.size()) return Err(SPM_INTERNAL, "final pieces do not fit the vocab");
-  if (spec_.hard_vocab_limit && static_cast<int>(out->size()) != spec_.vocab_size)
+  // CHAR is saved like hard_vocab_limit = false (trainer_interface.cc:516).
+  if (spec_.hard_vocab_limit && spec_.model_type != kChar && static_cast<int>(out->size()) != spec_.vocab_size)
     return Err(SPM_INTERNAL, "Vocabulary size too high (" + std::to_string(spec_.vocab_size) +
                                  "). Please set it to a value <= " + std::to_string(out->size()) + ".");
   return Status::Ok();
@@ -1892,7 +1928,7 @@ Status UnigramTrainer::Save() const {
   std::vector<PieceRec> pieces;
   RETURN_IF_ERROR(Serialize(&pieces));
   TrainerSpec ts = spec_;
-  if (!ts.hard_vocab_limit) {
+  if (!ts.hard_vocab_limit || ts.model_type == kChar) {
     ts.vocab_size = static_cast<int32_t>(pieces.size());
     ts.has.insert(4);
   }
@@ -2717,6 +2753,15 @@ Status UnigramTrainer::Train(TrainerTimings *tm) {
   t.load = t1 - t0;
   t.read = read_s_;
   stage_peak(0);
+  if (spec_.model_type == kChar) {  // char_model_trainer.cc:31-64
+    RETURN_IF_ERROR(TrainChar());
+    const double t4 = Now();
+    RETURN_IF_ERROR(Save());
+    t.finalize = Now() - t4;
+    t.total = Now() - t0;
+    stage_peak(3);
+    return Status::Ok();
+  }
   if (spec_.model_type == kBpe) {  // bpe_model_trainer.cc:185-330
     RETURN_IF_ERROR(TrainBpe(&t));
     const double t4 = Now();

@@ -10,6 +10,8 @@
 // T = num_threads ordered buckets, so results are bit-identical to the
 // reference at that thread count) and the pruning Viterbi over all sentences
 // (spm_hip_encode_batch on a TrainerModel built by spm_hip_model_from_pieces).
+// --model_type=char (character::Trainer, char_model_trainer.cc) needs only
+// the LoadSentences stage; --model_type=word is refused.
 #pragma once
 
 #include <cstdint>
