@@ -699,6 +699,18 @@ int spm_hip_bpe_census_view(const spm_hip_bpe_census *census, const uint32_t **c
  * position) views valid until the next call; the caller removes them from its
  * own sets.  Host pointers throughout; one call = one upload, one
  * synchronization.
+ *
+ * The order within a run() is writes, erases, inserts, todo.  So a position
+ * in both the erase and the insert list ends in the set, an erase of a
+ * position that is not in the set does nothing, and a position erased earlier
+ * (by the caller or by a refresh) may be inserted again: it is then in the set
+ * once.  Left to the caller: at most one write per flat index (they are
+ * scattered in parallel); the insert list sorted and free of duplicates, and
+ * no insert of a position that is in the device's set already (it would be
+ * held, and counted, twice); each symbol at most once in `todo`; every
+ * position inside its sentence.  A symbol without entries has freq 0.  With
+ * num_todo == 0 the changes are applied and *num_erased is 0.  Erased entries
+ * keep their slot, so num_entries of stats() only grows.
  * ------------------------------------------------------------------------ */
 typedef struct spm_hip_bpe_refresh spm_hip_bpe_refresh;
 int spm_hip_bpe_refresh_create(const int32_t *syms, const uint64_t *sent_offsets, const int64_t *sent_freq,

@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPM_AMD_LIB") or os.path.join(HERE, "lib", "libspm_hip.so")
 
 SPM_OK = 0
+SPM_INVALID_ARGUMENT = 3
 SPM_RESOURCE_EXHAUSTED = 8
 SPM_OUT_OF_RANGE = 11
 # Decode kernels (csrc/decode.h): tokens per tile, per sub-tile (one block
@@ -218,6 +219,21 @@ def lib():
         L.spm_hip_decode_batch_async.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, P, P]
         L.spm_hip_decode_batch_host.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, ctypes.POINTER(U64)]
         L.spm_hip_model_decode_bound.argtypes = [P, ctypes.POINTER(ctypes.c_uint32)]
+        L.spm_hip_bpe_pair_census.argtypes = [P, P, P, U64, ctypes.POINTER(P), P]
+        L.spm_hip_bpe_census_free.argtypes = [P]
+        L.spm_hip_bpe_census_free.restype = None
+        L.spm_hip_bpe_census_last_error.argtypes = []
+        L.spm_hip_bpe_census_last_error.restype = ctypes.c_char_p
+        L.spm_hip_bpe_census_view.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P),
+                                              ctypes.POINTER(U64), ctypes.POINTER(P), ctypes.POINTER(P),
+                                              ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(U64),
+                                              ctypes.POINTER(ctypes.c_float)]
+        L.spm_hip_bpe_refresh_create.argtypes = [P, P, P, U64, P, P, U64, P, ctypes.POINTER(P)]
+        L.spm_hip_bpe_refresh_run.argtypes = [P, P, U64, P, P, U64, P, P, U64, P, U64, P, ctypes.POINTER(P),
+                                              ctypes.POINTER(P), ctypes.POINTER(U64)]
+        L.spm_hip_bpe_refresh_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_float)]
+        L.spm_hip_bpe_refresh_free.argtypes = [P]
+        L.spm_hip_bpe_refresh_free.restype = None
         _lib = L
     return _lib
 
@@ -913,3 +929,130 @@ def seed_mine(sentences, chars, char_freq, max_sentencepiece_length=16, split_by
         return pieces, sc, {"num_chars": nc.value, "candidates": cand.value, "device_ms": ms.value}
     finally:
         L.spm_hip_seeds_free(h)
+
+
+def _copy_view(ptr, ctype, dtype, count):
+    """A numpy copy of `count` elements behind a library-owned pointer."""
+    if not count:
+        return np.zeros(0, dtype=dtype)
+    return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=(count,)).astype(dtype, copy=True)
+
+
+def bpe_pair_census(sentences, freqs):
+    """spm_hip_bpe_pair_census (the BPE trainer's char / pair census with the
+    first ComputeFreq, on the device).  sentences: list[bytes]; freqs: one
+    int64 per sentence.  Returns a dict of numpy copies of every view:
+    char_codes uint32 + char_offsets uint64[n + 1] (the decoded text, CSR),
+    unique_chars uint32 and pair_keys uint64 (left << 21 | right), both in
+    first-occurrence order, pair_freq uint64, pair_pos_offsets
+    uint64[num_pairs + 1] + pair_positions uint64 (kept EncodePos, ascending
+    per pair), and device_ms."""
+    import torch
+    L = lib()
+    n = len(sentences)
+    fr = np.ascontiguousarray(freqs, dtype=np.int64)
+    if len(fr) != n:
+        raise ValueError("bpe_pair_census needs one freq per sentence")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    buf, off = to_csr(list(sentences))
+    d_b = torch.from_numpy(buf).to(dev)
+    d_o = torch.from_numpy(off.view(np.int64)).to(dev)
+    d_f = torch.from_numpy(fr if n else np.zeros(1, dtype=np.int64)).to(dev)
+    s = torch.cuda.current_stream(dev).cuda_stream
+    P = ctypes.c_void_p
+    h = P()
+    rc = L.spm_hip_bpe_pair_census(P(d_b.data_ptr()), P(d_o.data_ptr()), P(d_f.data_ptr()), n, ctypes.byref(h),
+                                   P(s) if s else None)
+    if rc != SPM_OK:
+        raise SpmError(rc, L.spm_hip_bpe_census_last_error().decode(errors="replace"))
+    try:
+        codes, coff, uch, pk, pf, po, pp = P(), P(), P(), P(), P(), P(), P()
+        nuc, npairs, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_float()
+        rc = L.spm_hip_bpe_census_view(h, ctypes.byref(codes), ctypes.byref(coff), ctypes.byref(uch),
+                                       ctypes.byref(nuc), ctypes.byref(pk), ctypes.byref(pf), ctypes.byref(po),
+                                       ctypes.byref(pp), ctypes.byref(npairs), ctypes.byref(ms))
+        if rc != SPM_OK:
+            raise SpmError(rc, "spm_hip_bpe_census_view failed")
+        U32, U64 = ctypes.c_uint32, ctypes.c_uint64
+        char_offsets = _copy_view(coff, U64, np.uint64, n + 1)
+        pos_offsets = _copy_view(po, U64, np.uint64, npairs.value + 1)
+        return {
+            "char_codes": _copy_view(codes, U32, np.uint32, int(char_offsets[-1])),
+            "char_offsets": char_offsets,
+            "unique_chars": _copy_view(uch, U32, np.uint32, nuc.value),
+            "pair_keys": _copy_view(pk, U64, np.uint64, npairs.value),
+            "pair_freq": _copy_view(pf, U64, np.uint64, npairs.value),
+            "pair_pos_offsets": pos_offsets,
+            "pair_positions": _copy_view(pp, U64, np.uint64, int(pos_offsets[-1])),
+            "device_ms": ms.value,
+        }
+    finally:
+        L.spm_hip_bpe_census_free(h)
+
+
+class BpeRefresh:
+    """The BPE merge loop's device-resident pair-frequency refresh
+    (spm_hip_bpe_refresh).  syms: flat int32 symbol ids (-1 = merged away);
+    sent_offsets: uint64[n + 1]; sent_freq: int64[n]; pos_sym / pos_key: every
+    bigram's positions as (symbol id, EncodePos), sorted by (symbol,
+    position).  Host arrays throughout."""
+
+    def __init__(self, syms, sent_offsets, sent_freq, pos_sym, pos_key):
+        self._L = lib()
+        self.h = None
+        sy = np.ascontiguousarray(syms, dtype=np.int32)
+        so = np.ascontiguousarray(sent_offsets, dtype=np.uint64)
+        sf = np.ascontiguousarray(sent_freq, dtype=np.int64)
+        ps = np.ascontiguousarray(pos_sym, dtype=np.uint32)
+        pk = np.ascontiguousarray(pos_key, dtype=np.uint64)
+        if len(so) != len(sf) + 1 or len(ps) != len(pk) or len(sy) != int(so[-1]):
+            raise ValueError("BpeRefresh: array lengths do not agree")
+        h = ctypes.c_void_p()
+        rc = self._L.spm_hip_bpe_refresh_create(_p(sy), _p(so), _p(sf), len(sf), _p(ps), _p(pk), len(ps), None,
+                                                ctypes.byref(h))
+        self._check(rc)
+        self.h = h
+
+    def _check(self, rc):
+        if rc != SPM_OK:
+            raise SpmError(rc, self._L.spm_hip_bpe_census_last_error().decode(errors="replace"))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.spm_hip_bpe_refresh_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def run(self, writes, ins_sym, ins_key, del_sym, del_key, todo):
+        """spm_hip_bpe_refresh_run.  writes: uint64 (flat index << 32 | uint32
+        value), one per index; ins_*: inserted positions sorted by (symbol,
+        position); del_*: positions the caller erased; todo: uint32 triples
+        (symbol, left, right), flat or [k, 3].  Returns (freq uint64[k],
+        erased_sym uint32, erased_key uint64) as copies; the erased positions
+        come in no fixed order."""
+        w = np.ascontiguousarray(writes, dtype=np.uint64)
+        isym = np.ascontiguousarray(ins_sym, dtype=np.uint32)
+        ikey = np.ascontiguousarray(ins_key, dtype=np.uint64)
+        dsym = np.ascontiguousarray(del_sym, dtype=np.uint32)
+        dkey = np.ascontiguousarray(del_key, dtype=np.uint64)
+        td = np.ascontiguousarray(todo, dtype=np.uint32).reshape(-1)
+        if len(isym) != len(ikey) or len(dsym) != len(dkey) or len(td) % 3:
+            raise ValueError("BpeRefresh.run: array lengths do not agree")
+        nt = len(td) // 3
+        freq = np.zeros(nt, dtype=np.uint64)
+        es, ek, ne = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64()
+        self._check(self._L.spm_hip_bpe_refresh_run(
+            self.h, _p(w) if len(w) else None, len(w), _p(isym) if len(isym) else None,
+            _p(ikey) if len(ikey) else None, len(isym), _p(dsym) if len(dsym) else None,
+            _p(dkey) if len(dkey) else None, len(dsym), _p(td) if nt else None, nt, _p(freq) if nt else None,
+            ctypes.byref(es), ctypes.byref(ek), ctypes.byref(ne)))
+        return (freq, _copy_view(es, ctypes.c_uint32, np.uint32, ne.value),
+                _copy_view(ek, ctypes.c_uint64, np.uint64, ne.value))
+
+    def stats(self):
+        """spm_hip_bpe_refresh_stats: (entries held, alive or erased; device ms of all runs)."""
+        n, ms = ctypes.c_uint64(), ctypes.c_float()
+        self._check(self._L.spm_hip_bpe_refresh_stats(self.h, ctypes.byref(n), ctypes.byref(ms)))
+        return int(n.value), float(ms.value)
