@@ -780,6 +780,56 @@ int spm_hip_model_piece_lookup(const spm_hip_model *model, const uint8_t *bytes,
 int spm_hip_encode_raw_small_host(spm_hip_model *model, const uint8_t *raw, const uint64_t *raw_off,
                                   uint64_t n, int32_t *ids, uint64_t ids_cap, uint64_t *out_off);
 
+/* Vocabulary restriction (SentencePieceProcessor::SetVocabulary /
+ * ResetVocabulary, sentencepiece_processor.cc:203-245): piece types change
+ * on the loaded model, in place.  As in the reference, only the types
+ * change: the model built at load stays, so min_score / max_score and with
+ * them the unknown score (min_score - 10) and the USER_DEFINED node scores,
+ * the trie and the BPE pair and rank tables keep their load-time contents.
+ * A restricted handle is therefore NOT the handle of a model file whose types
+ * were edited.  Everything this engine derives from the types is brought up
+ * to date: max_piece_chars, the unigram kernel tier and ring width (get_info
+ * reports them), the near-tie bound, the cooperative kernel's switch (reset
+ * to its default rule), the kind bits and usable-node scores of the per-unit
+ * tables and the unused bit of the BPE pair entries (re-tagged on the device
+ * from one uploaded byte per piece), the byte kernel's piece table and the
+ * BPE per-piece kinds (rebuilt on the host).  The call waits for all work of
+ * this handle's streams, ends its resident small-call servers (the next small
+ * call restarts them) and returns when the tables are in place; it must not
+ * overlap any other call on the handle.  Works on host-only handles (info,
+ * piece_lookup and the host n-best tier follow).
+ *
+ * types: ModelProto::SentencePiece::Type per piece id (1 NORMAL, 2 UNKNOWN,
+ * 3 CONTROL, 4 USER_DEFINED, 5 UNUSED), n = piece_size.  Only NORMAL <->
+ * UNUSED changes are accepted: SPM_INVALID_ARGUMENT for any other change or a
+ * wrong n, and nothing is changed then. */
+int spm_hip_model_set_piece_types(spm_hip_model *model, const uint8_t *types, uint64_t n);
+int spm_hip_model_get_piece_types(const spm_hip_model *model, uint8_t *types, uint64_t n);
+/* SetVocabulary's rule over the model's own pieces: CONTROL, UNKNOWN and
+ * USER_DEFINED pieces stay; any other piece becomes NORMAL if it is one of
+ * the num_pieces given (CSR: piece_bytes, piece_offsets[num_pieces + 1]) or
+ * is one character long (OneCharLen(piece) == piece.size()), else UNUSED.
+ * UNIGRAM and BPE models only: otherwise SPM_INTERNAL "Vocabulary constraint
+ * is only enabled in subword units."  ResetVocabulary: every UNUSED piece
+ * becomes NORMAL, on any model type. */
+int spm_hip_model_set_vocabulary(spm_hip_model *model, const uint8_t *piece_bytes, const uint64_t *piece_offsets,
+                                 uint64_t num_pieces);
+int spm_hip_model_reset_vocabulary(spm_hip_model *model);
+
+/* Piece counting (spm_encode --generate_vocabulary, spm_encode_main.cc:
+ * 98-109): d_counts[id] += the occurrences of id in d_ids[0, num_tokens),
+ * d_counts = uint64[piece_size], accumulated over calls (zero it first).  An
+ * id outside [0, piece_size) is skipped, never used as an index, and sets bit
+ * 0 of *d_status (nullable).  Enqueued on `stream`, no host synchronization.
+ * Equal ids are summed on chip before global memory is touched: in
+ * per-workgroup LDS bins for up to 32768 pieces, else by a wave-level
+ * combine.  The _host form takes host pointers (counts is read, added to
+ * and written back; *status nullable) and blocks. */
+int spm_hip_count_ids(spm_hip_model *model, const int32_t *d_ids, uint64_t num_tokens, uint64_t *d_counts,
+                      uint32_t *d_status, void *stream);
+int spm_hip_count_ids_host(spm_hip_model *model, const int32_t *ids, uint64_t num_tokens, uint64_t *counts,
+                           uint32_t *status);
+
 /* Device memory this library holds in the calling process (every block it
  * allocates: models' workspaces, E-step piece sets, trainer corpus and
  * scratch): live bytes now and the high-water mark since the last reset.

@@ -23,9 +23,10 @@
 
 namespace spm_amd {
 
-// Per-stream encode workspace.  The model tables of a handle are immutable
-// after load; everything a call writes lives here, so concurrent calls on one
-// handle with different streams never share a buffer (the reference's
+// Per-stream encode workspace.  The model tables of a handle change only in
+// spm_hip_model_set_piece_types, which no other call may overlap; everything
+// a call writes lives here, so concurrent calls on one handle with different
+// streams never share a buffer (the reference's
 // unigram::Model::Encode is const with a stack-local Lattice,
 // unigram_model.cc:705-720).  A workspace is bound to one stream (device API)
 // or owns a private stream (host-buffer API); `mu` is held for a whole call.
@@ -62,6 +63,7 @@ struct EncodeWorkspace {
   // tile, first mark after each tile
   DevBuf w_wc_count, w_wc_first, w_wc_sent, w_wc_next;
   DevBuf w_tids, w_tlen, w_ttok;  // SentencePieceText path: raw ids, piece lengths, token offsets
+  DevBuf w_vstat, w_vcount;       // piece counting: status word; the host entry's counters
   DevBuf h_in, h_off, h_ids, h_len, h_tok;  // staging for the host API
   // Host API small batches (EncodeHostSmall): one device block [control |
   // offsets | bytes | tok | ids | len] and its pinned host mirror.
@@ -181,6 +183,7 @@ struct spm_hip_model {
   std::atomic<bool> norm_ready{false};
   uint32_t ud_units_n = 0;
   spm_amd::DevBuf d_types;
+  spm_amd::DevBuf d_types_kind;  // spm_hip_model_set_piece_types: per-piece kind bytes of the last re-tag
   std::atomic<bool> types_ready{false};
   // Decode table (decode.h), built at load; the device copy unless host_only.
   spm_amd::DecodeTable decode;

@@ -506,4 +506,23 @@ hipError_t LaunchWordCharTile(const WordCharLaunch &l, hipStream_t st);
 hipError_t LaunchWordCharGeneral(const WordCharLaunch &l, bool all, hipStream_t st);
 hipError_t LaunchWordCharOutput(const WordCharLaunch &l, hipStream_t st);
 
+// Vocabulary restriction and piece counting (vocab_kernels.hip).  kind: one
+// byte per piece id (0 other, kKindUserDefined, kKindUnused).
+// Unigram: the kind bits of every leaf's value and, when uvs is not null, the
+// usable-node score (the piece's score, NaN when UNUSED) of the (unit, score)
+// table; USER_DEFINED leaves are left alone.
+hipError_t LaunchVocabRetagUnigram(const uint32_t *units, int32_t *values, uint32_t *uvs, const float *scores,
+                                   const uint8_t *kind, uint32_t num_units, uint32_t num_pieces, hipStream_t st);
+// BPE: the unused bit of the merged piece in every pair entry (uint4 slots).
+hipError_t LaunchVocabRetagBpe(void *pair_ent, uint64_t slots, const uint8_t *kind, uint32_t num_pieces,
+                               hipStream_t st);
+// counts[id] += occurrences of id in ids[0, n), n <= 2^31 (the LDS bins are
+// 32 bits wide).  An id outside [0, num_pieces) is skipped and sets bit 0 of
+// *status.  Vocabularies of up to kCountLdsMaxPieces pieces are binned in
+// LDS per workgroup, kCountTile tokens per workgroup step.
+constexpr uint32_t kCountLdsMaxPieces = 32768;
+constexpr uint32_t kCountTile = 4096;
+hipError_t LaunchVocabCount(const int32_t *ids, uint64_t n, uint64_t *counts, uint32_t num_pieces, uint32_t *status,
+                            hipStream_t st);
+
 }  // namespace spm_amd

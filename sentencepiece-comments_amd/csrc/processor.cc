@@ -58,6 +58,13 @@ Status SentencePieceProcessor::Load(const std::string &filename) {
 }
 
 Status SentencePieceProcessor::LoadFromSerializedProto(const std::string &serialized) {
+  return LoadImpl(serialized, false);
+}
+
+Status SentencePieceProcessor::LoadHostOnly(const std::string &serialized) { return LoadImpl(serialized, true); }
+
+Status SentencePieceProcessor::LoadImpl(const std::string &serialized, bool host_only) {
+  host_only_ = host_only;
   spm_hip_model_free(model_);
   model_ = nullptr;
   proto_ = ModelProtoView();
@@ -67,7 +74,8 @@ Status SentencePieceProcessor::LoadFromSerializedProto(const std::string &serial
   if (!ParseModelProto(reinterpret_cast<const uint8_t *>(serialized.data()), serialized.size(),
                        &proto_, &err))
     return status_ = Err(SPM_INTERNAL, err);
-  Status st = FromC(spm_hip_model_load(serialized.data(), serialized.size(), &model_));
+  Status st = FromC(host_only ? spm_hip_model_load_host_only(serialized.data(), serialized.size(), &model_)
+                              : spm_hip_model_load(serialized.data(), serialized.size(), &model_));
   if (!st.ok()) return status_ = st;
   for (size_t i = 0; i < proto_.pieces.size(); ++i) {
     const auto &p = proto_.pieces[i];
@@ -78,7 +86,7 @@ Status SentencePieceProcessor::LoadFromSerializedProto(const std::string &serial
   // Self-test samples (sentencepiece_processor.cc:135-153).
   std::vector<std::string> inputs;
   for (const auto &s : proto_.self_test) inputs.push_back(s.first);
-  if (!inputs.empty()) {
+  if (!inputs.empty() && !host_only) {
     std::vector<std::vector<std::string>> got;
     Status e = EncodeBatch(inputs, nullptr, &got);
     if (!e.ok()) return status_ = e;
@@ -347,35 +355,21 @@ Status SentencePieceProcessor::SampleEncode(const std::string &input, int nbest_
   return st;
 }
 
-Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, std::vector<std::vector<int>> *ids,
-                                        std::vector<std::vector<std::string>> *pieces,
-                                        const SampleSpec *sample) const {
-  if (!status_.ok()) return status_;
+namespace {
+enum { kIn, kInOff, kNorm, kNormOff, kIds, kLen, kTok, kOut, kOutOff, kSmallBlockSlot, kCounts };
+}  // namespace
+
+// Raw lines -> device; Normalizer::Normalize and ModelInterface::Encode (or
+// the sampler) run on the device over the whole batch.  *b: the device
+// buffers of the normalized bytes and the model-level tokens.
+Status SentencePieceProcessor::DeviceEncode(const std::vector<std::string> &inputs, const SampleSpec *sample,
+                                            DeviceBatch *b) const {
   const uint64_t n = inputs.size();
-  // A WORD / CHAR model can return a CONTROL piece's id for a token (a word
-  // that spells it: PieceToId searches the reserved pieces first).  Such a
-  // token consumes no surface, so the reference fails the line ("all
-  // normalized characters are not consumed.").  The device id epilogue does
-  // not carry that check, so these models' ids take the host epilogue below.
-  const bool word_char = proto_.trainer_spec.model_type == kWord || proto_.trainer_spec.model_type == kChar;
-  if (!sample && !pieces && ids && !word_char && n >= 1 && n <= kSmallLines) {
-    uint64_t raw = 0;
-    for (const auto &s : inputs) raw += s.size();
-    if (raw <= kSmallBytes) {
-      bool done = false;
-      Status st = EncodeIdsSmall(inputs, ids, &done);
-      if (!st.ok() || done) return st;
-    }
-  }
   std::vector<uint64_t> in_off(n + 1, 0);
   for (uint64_t i = 0; i < n; ++i) in_off[i + 1] = in_off[i] + inputs[i].size();
   std::string in_bytes;
   in_bytes.reserve(in_off[n]);
   for (const auto &s : inputs) in_bytes += s;
-  // Raw lines → device; Normalizer::Normalize and ModelInterface::Encode run
-  // on the device over the whole batch; ids, piece lengths and (for piece
-  // output) the normalized bytes come back for the per-line epilogue.
-  enum { kIn, kInOff, kNorm, kNormOff, kIds, kLen, kTok };
   auto fail_hip = [](hipError_t e) { return Err(SPM_INTERNAL, hipGetErrorString(e)); };
   uint8_t *d_in = static_cast<uint8_t *>(dev_.Get(kIn, in_off[n]));
   uint64_t *d_in_off = static_cast<uint64_t *>(dev_.Get(kInOff, (n + 1) * 8));
@@ -406,19 +400,62 @@ Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, 
                                                   sample->index_base, d_ids, d_len, d_tok, nullptr)
                     : spm_hip_encode_batch(model_, d_norm, d_norm_off, n, d_ids, d_len, d_tok, nullptr));
   if (!st.ok()) return st;
+  *b = DeviceBatch{d_norm, d_norm_off, d_ids, d_len, d_tok, total};
+  return Status::Ok();
+}
+
+// The id epilogue of Encode(ids) on the device (spm_hip_finalize_ids: unknown
+// -run merge + extra options): the final ids, their offsets and their number.
+Status SentencePieceProcessor::DeviceFinalize(const DeviceBatch &b, uint64_t n, int32_t **d_out, uint64_t **d_out_off,
+                                              uint64_t *fin) const {
+  uint64_t n_extra = 0;
+  for (ExtraOption opt : extra_) n_extra += opt != REVERSE;
+  const uint64_t cap = b.total + n * n_extra;
+  *d_out_off = static_cast<uint64_t *>(dev_.Get(kOutOff, (n + 1) * 8));
+  *d_out = static_cast<int32_t *>(dev_.Get(kOut, std::max<uint64_t>(cap, 1) * 4));
+  if (!*d_out_off || !*d_out) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+  return FromC(spm_hip_finalize_ids(model_, extra_str_.c_str(), b.d_ids, b.d_tok, n, *d_out, cap, *d_out_off, fin,
+                                    nullptr));
+}
+
+Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, std::vector<std::vector<int>> *ids,
+                                        std::vector<std::vector<std::string>> *pieces,
+                                        const SampleSpec *sample) const {
+  if (!status_.ok()) return status_;
+  if (host_only_) return Err(SPM_FAILED_PRECONDITION, "host-only processor");
+  const uint64_t n = inputs.size();
+  // A WORD / CHAR model can return a CONTROL piece's id for a token (a word
+  // that spells it: PieceToId searches the reserved pieces first).  Such a
+  // token consumes no surface, so the reference fails the line ("all
+  // normalized characters are not consumed.").  The device id epilogue does
+  // not carry that check, so these models' ids take the host epilogue below.
+  const bool word_char = proto_.trainer_spec.model_type == kWord || proto_.trainer_spec.model_type == kChar;
+  if (!sample && !pieces && ids && !word_char && n >= 1 && n <= kSmallLines) {
+    uint64_t raw = 0;
+    for (const auto &s : inputs) raw += s.size();
+    if (raw <= kSmallBytes) {
+      bool done = false;
+      Status st = EncodeIdsSmall(inputs, ids, &done);
+      if (!st.ok() || done) return st;
+    }
+  }
+  auto fail_hip = [](hipError_t e) { return Err(SPM_INTERNAL, hipGetErrorString(e)); };
+  hipError_t he;
+  DeviceBatch b;
+  Status st = DeviceEncode(inputs, sample, &b);
+  if (!st.ok()) return st;
+  uint8_t *d_norm = b.d_norm;
+  uint64_t *d_norm_off = b.d_norm_off, *d_tok = b.d_tok;
+  int32_t *d_ids = b.d_ids;
+  uint32_t *d_len = b.d_len;
+  const uint64_t total = b.total;
   if (!pieces && !word_char) {
     // Encode(ids): the id epilogue (unk-run merge + extra options) runs on the
     // device as well (spm_hip_finalize_ids); only the final ids come back.
-    enum { kOut = 7, kOutOff = 8 };
-    uint64_t n_extra = 0;
-    for (ExtraOption opt : extra_) n_extra += opt != REVERSE;
-    const uint64_t cap = total + n * n_extra;
-    uint64_t *d_out_off = static_cast<uint64_t *>(dev_.Get(kOutOff, (n + 1) * 8));
-    int32_t *d_out = static_cast<int32_t *>(dev_.Get(kOut, std::max<uint64_t>(cap, 1) * 4));
-    if (!d_out_off || !d_out) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+    int32_t *d_out = nullptr;
+    uint64_t *d_out_off = nullptr;
     uint64_t fin = 0;
-    st = FromC(spm_hip_finalize_ids(model_, extra_str_.c_str(), d_ids, d_tok, n, d_out, cap, d_out_off, &fin,
-                                    nullptr));
+    st = DeviceFinalize(b, n, &d_out, &d_out_off, &fin);
     if (!st.ok()) return st;
     std::vector<uint64_t> out_off(n + 1);
     std::vector<int32_t> out(std::max<uint64_t>(fin, 1));
@@ -456,6 +493,102 @@ Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, 
     if (pieces)
       for (auto &p : spt) (*pieces)[i].push_back(std::move(p.first));
   }
+  return Status::Ok();
+}
+
+// SetVocabulary / ResetVocabulary / LoadVocabulary (sentencepiece_processor.cc:
+// 203-274).  The rule runs in the C-ABI over the handle's pieces, which are
+// this proto's; the resulting types come back into proto_, so IsUnused and
+// Encode agree.
+Status SentencePieceProcessor::SyncTypes() {
+  std::vector<uint8_t> types(proto_.pieces.size());
+  const Status st = FromC(spm_hip_model_get_piece_types(model_, types.data(), types.size()));
+  if (!st.ok()) return st;
+  for (size_t i = 0; i < types.size(); ++i) proto_.pieces[i].type = types[i];
+  return Status::Ok();
+}
+
+Status SentencePieceProcessor::SetVocabulary(const std::vector<std::string> &valid_vocab) {
+  if (!status_.ok()) return status_;
+  std::vector<uint64_t> off(valid_vocab.size() + 1, 0);
+  std::string bytes;
+  for (size_t i = 0; i < valid_vocab.size(); ++i) {
+    bytes += valid_vocab[i];
+    off[i + 1] = bytes.size();
+  }
+  const Status st = FromC(spm_hip_model_set_vocabulary(model_, reinterpret_cast<const uint8_t *>(bytes.data()),
+                                                       off.data(), valid_vocab.size()));
+  return st.ok() ? SyncTypes() : st;
+}
+
+Status SentencePieceProcessor::ResetVocabulary() {
+  if (!status_.ok()) return status_;
+  const Status st = FromC(spm_hip_model_reset_vocabulary(model_));
+  return st.ok() ? SyncTypes() : st;
+}
+
+Status SentencePieceProcessor::LoadVocabulary(const std::string &filename, int threshold) {
+  std::ifstream in(filename, std::ios::binary);
+  if (!in) return Err(SPM_NOT_FOUND, "\"" + filename + "\": No such file or directory");
+  std::vector<std::string> vocab;
+  std::string line;
+  while (std::getline(in, line)) {
+    // string_util::Split(line, "\t") (util.cc:32-49): empty fields are
+    // dropped, so an empty line (or one of tabs only) has no field at all.
+    std::vector<std::string> v;
+    for (size_t at = 0; at <= line.size();) {
+      const size_t e = std::min(line.find('\t', at), line.size());
+      if (e > at) v.push_back(line.substr(at, e - at));
+      at = e + 1;
+    }
+    if (v.empty()) return Err(SPM_INTERNAL, "[(v.size()) >= (1)] ");
+    if (v[0].empty()) return Err(SPM_INTERNAL, "[!v[0].empty()] ");
+    int freq = 1;
+    if (v.size() >= 2) freq = std::atoi(v[1].c_str());
+    if (freq >= threshold) vocab.push_back(v[0]);
+  }
+  return SetVocabulary(vocab);
+}
+
+// Piece frequencies of a batch: normalize, encode, the id epilogue and the
+// count (spm_hip_count_ids) run on the device; only the counters come back.
+Status SentencePieceProcessor::CountPieces(const std::vector<std::string> &inputs,
+                                           std::vector<uint64_t> *counts) const {
+  if (!status_.ok()) return status_;
+  if (!counts) return Err(SPM_INTERNAL, "output container is null");
+  const uint64_t n = inputs.size(), v = proto_.pieces.size();
+  counts->resize(v, 0);
+  if (n == 0) return Status::Ok();
+  std::vector<uint64_t> add(v, 0);
+  const bool word_char = proto_.trainer_spec.model_type == kWord || proto_.trainer_spec.model_type == kChar;
+  if (word_char) {
+    // These models' ids take the host epilogue (RunBatch); their ids go back up.
+    std::vector<std::vector<int>> ids;
+    Status st = RunBatch(inputs, &ids, nullptr, nullptr);
+    if (!st.ok()) return st;
+    std::vector<int32_t> flat;
+    for (const auto &row : ids) flat.insert(flat.end(), row.begin(), row.end());
+    st = FromC(spm_hip_count_ids_host(model_, flat.data(), flat.size(), add.data(), nullptr));
+    if (!st.ok()) return st;
+  } else {
+    DeviceBatch b;
+    Status st = DeviceEncode(inputs, nullptr, &b);
+    if (!st.ok()) return st;
+    int32_t *d_out = nullptr;
+    uint64_t *d_out_off = nullptr;
+    uint64_t fin = 0;
+    st = DeviceFinalize(b, n, &d_out, &d_out_off, &fin);
+    if (!st.ok()) return st;
+    uint64_t *d_counts = static_cast<uint64_t *>(dev_.Get(kCounts, v * 8));
+    if (!d_counts) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+    hipError_t he;
+    if ((he = hipMemset(d_counts, 0, v * 8)) != hipSuccess) return Err(SPM_INTERNAL, hipGetErrorString(he));
+    st = FromC(spm_hip_count_ids(model_, d_out, fin, d_counts, nullptr, nullptr));
+    if (!st.ok()) return st;
+    if ((he = hipMemcpy(add.data(), d_counts, v * 8, hipMemcpyDeviceToHost)) != hipSuccess)
+      return Err(SPM_INTERNAL, hipGetErrorString(he));
+  }
+  for (uint64_t i = 0; i < v; ++i) (*counts)[i] += add[i];
   return Status::Ok();
 }
 

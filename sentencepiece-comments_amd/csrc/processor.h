@@ -42,6 +42,11 @@ class SentencePieceProcessor {
 
   Status Load(const std::string &filename);
   Status LoadFromSerializedProto(const std::string &serialized);
+  // Tables only, nothing on the device (spm_hip_model_load_host_only): the
+  // piece queries and the three vocabulary calls work, every encode and decode
+  // call is an error and the model's self-test samples are not run.  For tools
+  // and tests on machines without a GPU.
+  Status LoadHostOnly(const std::string &serialized);
   Status status() const;
 
   // "bos", "eos", "reverse" separated by ':' (sentencepiece_processor.cc:981-1010).
@@ -87,6 +92,29 @@ class SentencePieceProcessor {
                           std::vector<std::vector<std::vector<int>>> *ids,
                           std::vector<std::vector<std::vector<std::string>>> *pieces,
                           std::vector<std::vector<float>> *scores) const;
+
+  // Vocabulary restriction (sentencepiece_processor.cc:203-274), with the
+  // reference's names, errors and results.  SetVocabulary (UNIGRAM and BPE
+  // models only): CONTROL, UNKNOWN and USER_DEFINED pieces stay, any other
+  // piece becomes NORMAL if it is in valid_vocab or one character long, else
+  // UNUSED.  ResetVocabulary: every UNUSED piece becomes NORMAL, those UNUSED
+  // in the model file included.  LoadVocabulary: "piece[\tfreq]" lines (freq
+  // defaults to 1), pieces with freq >= threshold go to SetVocabulary.  As in
+  // the reference only the types change: the scores the model took at Load
+  // (the unknown score among them) stay, so a restricted processor is not the
+  // processor of a model file whose types were edited.  proto_ and the device
+  // model change together (spm_hip_model_set_piece_types), so every encode
+  // call that follows sees the restriction.  Not for use concurrently with
+  // any other call on the instance.
+  Status SetVocabulary(const std::vector<std::string> &valid_vocab);
+  Status ResetVocabulary();
+  Status LoadVocabulary(const std::string &filename, int threshold);
+
+  // counts[id] += the occurrences of id in Encode(line, &ids) of every input
+  // line (extra options applied; counts grows to GetPieceSize()).  Normalize,
+  // encode, id epilogue and count run on the device (spm_hip_count_ids); only
+  // the counters come back.  Accumulates over calls.
+  Status CountPieces(const std::vector<std::string> &inputs, std::vector<uint64_t> *counts) const;
 
   // Decode (sentencepiece_processor.cc:341-370, :670-733).  One piece of
   // SentencePieceText: surface = text[begin, end).
@@ -162,6 +190,21 @@ class SentencePieceProcessor {
     float theta;
     uint64_t seed, index_base;
   };
+  Status LoadImpl(const std::string &serialized, bool host_only);
+  bool host_only_ = false;
+  Status SyncTypes();  // the handle's piece types -> proto_
+  // A batch on the device after normalize + encode (DeviceEncode), and its id
+  // epilogue (DeviceFinalize); the buffers are dev_'s.
+  struct DeviceBatch {
+    uint8_t *d_norm = nullptr;
+    uint64_t *d_norm_off = nullptr;
+    int32_t *d_ids = nullptr;
+    uint32_t *d_len = nullptr;
+    uint64_t *d_tok = nullptr;
+    uint64_t total = 0;  // normalized bytes
+  };
+  Status DeviceEncode(const std::vector<std::string> &inputs, const SampleSpec *sample, DeviceBatch *b) const;
+  Status DeviceFinalize(const DeviceBatch &b, uint64_t n, int32_t **d_out, uint64_t **d_out_off, uint64_t *fin) const;
   // EncodeBatch; with `sample` the device sampler stands in for the encode.
   Status RunBatch(const std::vector<std::string> &inputs, std::vector<std::vector<int>> *ids,
                   std::vector<std::vector<std::string>> *pieces, const SampleSpec *sample) const;
@@ -170,8 +213,8 @@ class SentencePieceProcessor {
                       uint64_t count, std::vector<std::pair<std::string, int>> *out) const;
   // Grow-only device staging for EncodeBatch (raw lines → normalized → ids).
   struct Staging {
-    void *ptr[10] = {};
-    size_t cap[10] = {};
+    void *ptr[11] = {};
+    size_t cap[11] = {};
     void *Get(int k, size_t bytes);
     ~Staging();
   };

@@ -9,6 +9,15 @@
 // line, best first.  --random_seed (not in the reference) makes a run
 // reproducible.
 //
+// --vocabulary / --vocabulary_threshold (spm_encode_main.cc:70-72) restrict
+// the pieces the encoder emits (SentencePieceProcessor::LoadVocabulary), and
+// --generate_vocabulary (:98-109, :196-201) writes "piece\tcount" lines
+// instead of a segmentation: every emitted piece that is neither unknown nor
+// control, by count descending, then piece ascending.  The pieces are counted
+// on the device (SentencePieceProcessor::CountPieces).  Counts are 64-bit
+// here: the reference's int would overflow on the corpora this engine is
+// meant for; below 2^31 the output is byte-identical to the reference's.
+//
 // The reference encodes one line at a time (spm_encode_main.cc:189-191).
 // Here lines are read in batches (--batch_lines), normalized and encoded on
 // the device in one call per batch (SentencePieceProcessor::EncodeBatch;
@@ -16,6 +25,8 @@
 // one output line per input line, pieces / ids joined by " ".  Lines are
 // read with std::getline semantics (a trailing '\r' is kept,
 // filesystem.cc:42-44).
+#include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -28,7 +39,9 @@
 namespace {
 
 struct Flags {
-  std::string model, output_format = "piece", output, extra_options;
+  std::string model, output_format = "piece", output, extra_options, vocabulary;
+  int vocabulary_threshold = 0;
+  bool generate_vocabulary = false;
   long batch_lines = 1 << 20;
   int nbest_size = 10;
   float alpha = 0.5f;
@@ -48,6 +61,12 @@ void Usage(const char *argv0) {
                "whole lattice, 0 or 1 is the best segmentation, larger values are not implemented)  "
                "type: int32 default: 10\n"
             << "   --alpha (smoothing parameter for sampling mode)  type: double default: 0.5\n"
+            << "   --vocabulary (Restrict the vocabulary. The encoder only emits the tokens in \"vocabulary\" "
+               "file)  type: string default: \n"
+            << "   --vocabulary_threshold (Words with frequency < threshold will be treated as OOV)  "
+               "type: int32 default: 0\n"
+            << "   --generate_vocabulary (Generates vocabulary file instead of segmentation)  "
+               "type: bool default: false\n"
             << "   --random_seed (seed of the sampler; unset: random)  type: uint64 default: \n"
             << "   --batch_lines (lines per device batch)  type: int64 default: 1048576\n";
 }
@@ -112,6 +131,16 @@ int main(int argc, char **argv) {
     } else if (k == "random_seed") {
       f.has_seed = true;
       f.random_seed = std::strtoull(v.c_str(), nullptr, 10);
+    } else if (k == "vocabulary") {
+      f.vocabulary = v;
+    } else if (k == "vocabulary_threshold") {
+      f.vocabulary_threshold = std::atoi(v.c_str());
+    } else if (k == "generate_vocabulary") {
+      // A boolean takes no separate value: a word after the bare flag that is
+      // no boolean is an input file.
+      const bool no = v == "false" || v == "0" || v == "f" || v == "no";
+      f.generate_vocabulary = !no;
+      if (!no && v != "true" && v != "1" && v != "t" && v != "yes") rest.push_back(v);
     } else if (k == "minloglevel") {
     } else {
       Usage(argv[0]);
@@ -125,7 +154,7 @@ int main(int argc, char **argv) {
   const bool sample = f.output_format == "sample_id" || f.output_format == "sample_piece";
   const bool nbest = f.output_format == "nbest_id" || f.output_format == "nbest_piece";
   const bool want_ids = f.output_format == "id" || f.output_format == "sample_id" || f.output_format == "nbest_id";
-  if (!sample && !nbest && f.output_format != "id" && f.output_format != "piece")
+  if (!f.generate_vocabulary && !sample && !nbest && f.output_format != "id" && f.output_format != "piece")
     Die("output_format \"" + f.output_format +
         "\": only piece, id, sample_piece, sample_id, nbest_piece and nbest_id are implemented by the device "
         "engine");
@@ -136,6 +165,10 @@ int main(int argc, char **argv) {
   st = sp.SetEncodeExtraOptions(f.extra_options);
   if (!st.ok()) Die(st.message);
   if (f.has_seed) sp.SetRandomSeed(f.random_seed);
+  if (!f.vocabulary.empty()) {
+    st = sp.LoadVocabulary(f.vocabulary, f.vocabulary_threshold);
+    if (!st.ok()) Die(st.message);
+  }
 
   std::ofstream ofs;
   std::ostream *out = &std::cout;
@@ -152,8 +185,15 @@ int main(int argc, char **argv) {
   std::vector<std::vector<std::vector<int>>> nbest_ids;
   std::vector<std::vector<std::vector<std::string>>> nbest_pieces;
   std::string buf;
+  std::vector<uint64_t> counts;
   auto flush = [&]() {
     if (batch.empty()) return;
+    if (f.generate_vocabulary) {
+      auto s = sp.CountPieces(batch, &counts);
+      if (!s.ok()) Die(s.message);
+      batch.clear();
+      return;
+    }
     if (nbest) {
       auto s = sp.NBestEncodeBatch(batch, f.nbest_size, want_ids ? &nbest_ids : nullptr,
                                    want_ids ? nullptr : &nbest_pieces, nullptr);
@@ -217,5 +257,18 @@ int main(int argc, char **argv) {
     }
   }
   flush();
+  if (f.generate_vocabulary) {
+    std::vector<std::pair<std::string, uint64_t>> vocab;
+    for (size_t id = 0; id < counts.size(); ++id)
+      if (counts[id] && !sp.IsUnknown(static_cast<int>(id)) && !sp.IsControl(static_cast<int>(id)))
+        vocab.emplace_back(sp.IdToPiece(static_cast<int>(id)), counts[id]);
+    std::sort(vocab.begin(), vocab.end(), [](const auto &a, const auto &b) {
+      return a.second > b.second || (a.second == b.second && a.first < b.first);
+    });
+    for (const auto &it : vocab) {
+      buf = it.first + "\t" + std::to_string(it.second) + "\n";
+      out->write(buf.data(), buf.size());
+    }
+  }
   return 0;
 }

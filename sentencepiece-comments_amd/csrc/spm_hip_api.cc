@@ -211,19 +211,14 @@ std::vector<uint32_t> BuildPieceTable(const spm_hip_model *m, const std::vector<
   return {};
 }
 
-// unigram::Model::Model (unigram_model.cc:677-695) + BuildTrie (:624-673).
-int LoadUnigram(spm_hip_model *m) {
-  m->min_score = FLT_MAX;
-  m->max_score = FLT_MIN;
-  for (const auto &sp : m->proto.pieces)
-    if (sp.type == spm_amd::kNormal) {
-      m->min_score = std::min(m->min_score, sp.score);
-      m->max_score = std::max(m->max_score, sp.score);
-    }
-  if (m->proto.pieces.size() >= static_cast<size_t>(spm_amd::kIdMask))
-    return Fail(SPM_RESOURCE_EXHAUSTED, "too many pieces for the device trie");
-  std::vector<std::pair<std::string, int32_t>> keys;
-  keys.reserve(m->pieces.size());
+// Unigram state that follows the piece types (LoadUnigram, and again after
+// spm_hip_model_set_piece_types): the piece-length bounds, the kernel tier
+// and its switches, tie_mag, the usable-node scores and the byte kernel's
+// piece table.  The trie, min_score / max_score and with them up.unk_score
+// and up.max_score are the load's and are not touched (the reference keeps
+// the model object it built at Load, sentencepiece_processor.cc:203-245).
+// vbp: the usable-node scores (empty when the tier has no pair table).
+void DeriveUnigram(spm_hip_model *m, std::vector<float> *vbp) {
   int max_chars = 0;
   size_t max_bytes = 0;
   bool split_ok = true;
@@ -231,10 +226,6 @@ int LoadUnigram(spm_hip_model *m) {
   for (const auto &kv : m->pieces) {
     const int32_t id = kv.second;
     const int32_t type = m->proto.pieces[id].type;
-    int32_t kind = 0;
-    if (type == spm_amd::kUserDefined) kind = spm_amd::kKindUserDefined;
-    if (type == spm_amd::kUnused) kind = spm_amd::kKindUnused;
-    keys.emplace_back(kv.first, id | (kind << spm_amd::kKindShift));
     if (type != spm_amd::kUnused) {
       // C-string key semantics: count chars up to the first NUL.
       std::string k = kv.first.substr(0, kv.first.find('\0'));
@@ -248,26 +239,14 @@ int LoadUnigram(spm_hip_model *m) {
     }
     if (type == spm_amd::kNormal) tie_mag = std::max(tie_mag, std::fabs(m->proto.pieces[id].score));
   }
-  if (keys.empty()) return Fail(SPM_INTERNAL, "no pieces are loaded.");
-  std::string err;
-  if (!spm_amd::BuildDoubleArray(std::move(keys), &m->trie, &err)) return Fail(SPM_RESOURCE_EXHAUSTED, err);
-  if (m->trie.max_prefix_matches == 0) return Fail(SPM_INTERNAL, "no entry is found in the trie.");
   m->max_piece_chars = max_chars;
   m->max_piece_bytes = static_cast<int32_t>(max_bytes);
-  const float unk_score = m->min_score - 10.0f;  // kUnkPenalty (unigram_model.cc:563)
-  tie_mag = std::max(tie_mag, std::fabs(unk_score));
+  tie_mag = std::max(tie_mag, std::fabs(m->up.unk_score));
   tie_mag = std::max(tie_mag, std::fabs(static_cast<float>(max_chars) * m->max_score) + 1.0f);
-  m->up.root_base = spm_amd::DoubleArray::Base(m->trie.units[0]);
-  m->up.unk_id = m->unk_id;
-  m->up.unk_score = unk_score;
-  m->up.max_score = m->max_score;
   m->up.tie_mag = tie_mag + 1.0f;
-  m->up.trie_results_size = m->trie.max_prefix_matches;
   // The fast kernel's ring is indexed by byte distance: W > longest piece in bytes.
   m->ring_width = max_bytes < 16 ? 16 : max_bytes < 32 ? 32 : max_bytes < 64 ? 64 : 0;
-  std::vector<float> scores(m->proto.pieces.size());
-  for (size_t i = 0; i < scores.size(); ++i) scores[i] = m->proto.pieces[i].score;
-  m->host_scores = scores;
+  const std::vector<float> &scores = m->host_scores;
   bool nan_score = false;
   for (size_t u = 0; u < m->trie.units.size(); ++u) {
     if (!spm_amd::DoubleArray::Leaf(m->trie.units[u])) continue;
@@ -293,34 +272,85 @@ int LoadUnigram(spm_hip_model *m) {
   // lane kernels' path.
   m->coop_min_nb = (nan_score || max_bytes > 56) ? 0u : DefaultCoopMinNb();
   const bool pair_table = byte_ok || wide_ok || (m->kernel == spm_amd::UnigramKernel::kChar && !nan_score);
+  vbp->clear();
+  if (pair_table) *vbp = UsableNodeScores(m, scores);
+  m->piece_table.clear();
+  if (byte_ok) m->piece_table = BuildPieceTable(m, *vbp);
+}
+
+// The (unit, score) table of the byte / wide / char / cooperative kernels.
+int UploadUnitScores(spm_hip_model *m, const std::vector<float> &vbp) {
+  // Empty units get label 0xFF so a walk needs no NUL test: real labels
+  // are never 0 (keys stop at NUL) and a 0xFF input byte flags the sentence.
+  // The root (unit 0, label 0) gets 0xFF too: a childless node has base 0,
+  // so an input NUL after it would otherwise step onto the root and match.
+  std::vector<uint32_t> ff = m->trie.units;
+  for (size_t u = 1; u < ff.size(); ++u)
+    if (ff[u] == 0) ff[u] = 0xFFu;
+  if (!ff.empty()) ff[0] |= 0xFFu;
+  // One (unit, score) pair per unit: the walk reads both with one 8-byte
+  // gather per step.
+  std::vector<uint32_t> uvs(2 * ff.size());
+  for (size_t u = 0; u < ff.size(); ++u) {
+    uvs[2 * u] = ff[u];
+    std::memcpy(&uvs[2 * u + 1], &vbp[u], 4);
+  }
+  SPM_HIP_TRY(Upload(&m->d_uvs, uvs));
+  return SPM_OK;
+}
+
+// The backtrace's piece table (A/B knob: SPM_HIP_NO_PIECE_TABLE leaves the
+// pointer null and the kernel re-walks the trie).
+int UploadPieceTable(spm_hip_model *m) {
+  if (!m->piece_table.empty() && std::getenv("SPM_HIP_NO_PIECE_TABLE") == nullptr)
+    SPM_HIP_TRY(Upload(&m->d_piece_tab, m->piece_table));
+  else
+    m->d_piece_tab.Release();
+  return SPM_OK;
+}
+
+// unigram::Model::Model (unigram_model.cc:677-695) + BuildTrie (:624-673).
+int LoadUnigram(spm_hip_model *m) {
+  m->min_score = FLT_MAX;
+  m->max_score = FLT_MIN;
+  for (const auto &sp : m->proto.pieces)
+    if (sp.type == spm_amd::kNormal) {
+      m->min_score = std::min(m->min_score, sp.score);
+      m->max_score = std::max(m->max_score, sp.score);
+    }
+  if (m->proto.pieces.size() >= static_cast<size_t>(spm_amd::kIdMask))
+    return Fail(SPM_RESOURCE_EXHAUSTED, "too many pieces for the device trie");
+  std::vector<std::pair<std::string, int32_t>> keys;
+  keys.reserve(m->pieces.size());
+  for (const auto &kv : m->pieces) {
+    const int32_t id = kv.second;
+    const int32_t type = m->proto.pieces[id].type;
+    int32_t kind = 0;
+    if (type == spm_amd::kUserDefined) kind = spm_amd::kKindUserDefined;
+    if (type == spm_amd::kUnused) kind = spm_amd::kKindUnused;
+    keys.emplace_back(kv.first, id | (kind << spm_amd::kKindShift));
+  }
+  if (keys.empty()) return Fail(SPM_INTERNAL, "no pieces are loaded.");
+  std::string err;
+  if (!spm_amd::BuildDoubleArray(std::move(keys), &m->trie, &err)) return Fail(SPM_RESOURCE_EXHAUSTED, err);
+  if (m->trie.max_prefix_matches == 0) return Fail(SPM_INTERNAL, "no entry is found in the trie.");
+  m->up.root_base = spm_amd::DoubleArray::Base(m->trie.units[0]);
+  m->up.unk_id = m->unk_id;
+  m->up.unk_score = m->min_score - 10.0f;  // kUnkPenalty (unigram_model.cc:563)
+  m->up.max_score = m->max_score;
+  m->up.trie_results_size = m->trie.max_prefix_matches;
+  m->host_scores.resize(m->proto.pieces.size());
+  for (size_t i = 0; i < m->host_scores.size(); ++i) m->host_scores[i] = m->proto.pieces[i].score;
   std::vector<float> vbp;
-  if (pair_table) vbp = UsableNodeScores(m, scores);
-  if (byte_ok) m->piece_table = BuildPieceTable(m, vbp);
+  DeriveUnigram(m, &vbp);
   if (m->host_only) return SPM_OK;
   SPM_HIP_TRY(Upload(&m->d_units, m->trie.units));
   SPM_HIP_TRY(Upload(&m->d_values, m->trie.values));
-  SPM_HIP_TRY(Upload(&m->d_scores, scores));
-  if (pair_table) {
-    // Empty units get label 0xFF so a walk needs no NUL test: real labels
-    // are never 0 (keys stop at NUL) and a 0xFF input byte flags the sentence.
-    // The root (unit 0, label 0) gets 0xFF too: a childless node has base 0,
-    // so an input NUL after it would otherwise step onto the root and match.
-    std::vector<uint32_t> ff = m->trie.units;
-    for (size_t u = 1; u < ff.size(); ++u)
-      if (ff[u] == 0) ff[u] = 0xFFu;
-    if (!ff.empty()) ff[0] |= 0xFFu;
-    // One (unit, score) pair per unit: the walk reads both with one 8-byte
-    // gather per step.
-    std::vector<uint32_t> uvs(2 * ff.size());
-    for (size_t u = 0; u < ff.size(); ++u) {
-      uvs[2 * u] = ff[u];
-      std::memcpy(&uvs[2 * u + 1], &vbp[u], 4);
-    }
-    SPM_HIP_TRY(Upload(&m->d_uvs, uvs));
-    // The backtrace's piece table (A/B knob: SPM_HIP_NO_PIECE_TABLE leaves the
-    // pointer null and the kernel re-walks the trie).
-    if (!m->piece_table.empty() && std::getenv("SPM_HIP_NO_PIECE_TABLE") == nullptr)
-      SPM_HIP_TRY(Upload(&m->d_piece_tab, m->piece_table));
+  SPM_HIP_TRY(Upload(&m->d_scores, m->host_scores));
+  if (!vbp.empty()) {
+    int rc = UploadUnitScores(m, vbp);
+    if (rc == SPM_OK) rc = UploadPieceTable(m);
+    if (rc != SPM_OK) return rc;
   }
   return SPM_OK;
 }
@@ -1096,7 +1126,7 @@ void EncodeWorkspace::Release() {
                     &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_dfirst, &w_dsum, &w_dctl, &h_dids, &h_dtok, &h_dout, &h_doff, &h_dbegin, &w_tids, &w_tlen, &w_ttok,
                     &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask,
                     &w_nb_ctl, &w_nb_npaths, &w_nb_stage, &w_nb_ntok, &w_nb_score, &w_nb_ids, &w_nb_len, &w_nb_hids,
-                    &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore, &w_wc_count, &w_wc_first, &w_wc_sent, &w_wc_next})
+                    &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore, &w_wc_count, &w_wc_first, &w_wc_sent, &w_wc_next, &w_vstat, &w_vcount})
     b->Release();
   if (pinned) (void)hipHostFree(pinned);
   pinned = nullptr;
@@ -1318,7 +1348,7 @@ void spm_hip_model_free(spm_hip_model *m) {
   for (spm_amd::DevBuf *b : {&m->d_units, &m->d_uvs, &m->d_piece_tab, &m->d_values, &m->d_scores,
                              &m->bpe.pair_keys, &m->bpe.pair_vals, &m->bpe.pair_ent, &m->bpe.rank_piece, &m->bpe.entry_piece,
                              &m->bpe.entry_out, &m->bpe.piece_kind, &m->bpe.piece_out,
-                             &m->d_wc_tab, &m->d_wc_keys, &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes})
+                             &m->d_wc_tab, &m->d_wc_keys, &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_types_kind, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes})
     b->Release();
   for (auto &kv : m->by_stream) kv.second->Release();
   for (auto &w : m->host_pool) w->Release();
@@ -3103,6 +3133,182 @@ int spm_hip_model_decode_bound(const spm_hip_model *m, uint32_t *max_surface_byt
   if (!m || !max_surface_bytes) return Fail(SPM_INVALID_ARGUMENT, "null argument");
   if (m->decode.meta.empty()) return Fail(SPM_FAILED_PRECONDITION, "model has no decode table");
   *max_surface_bytes = m->decode.max_surface;
+  return SPM_OK;
+}
+
+// ---- Vocabulary restriction (sentencepiece_processor.cc:203-245) ----
+
+int spm_hip_model_get_piece_types(const spm_hip_model *m, uint8_t *types, uint64_t n) {
+  if (!m || !types) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (n != m->proto.pieces.size()) return Fail(SPM_INVALID_ARGUMENT, "n is not the model's piece_size");
+  for (uint64_t i = 0; i < n; ++i) types[i] = static_cast<uint8_t>(m->proto.pieces[i].type);
+  return SPM_OK;
+}
+
+int spm_hip_model_set_piece_types(spm_hip_model *m, const uint8_t *types, uint64_t n) {
+  spm_amd::TraceRange trace_range_("spm_hip_model_set_piece_types");
+  if (!m || !types) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  auto &pieces = m->proto.pieces;
+  if (n != pieces.size()) return Fail(SPM_INVALID_ARGUMENT, "n is not the model's piece_size");
+  bool changed = false;
+  for (uint64_t i = 0; i < n; ++i) {
+    const int32_t was = pieces[i].type, now = types[i];
+    if (was == now) continue;
+    const bool free_was = was == spm_amd::kNormal || was == spm_amd::kUnused;
+    const bool free_now = now == spm_amd::kNormal || now == spm_amd::kUnused;
+    if (!free_was || !free_now)
+      return Fail(SPM_INVALID_ARGUMENT, "piece " + std::to_string(i) + ": only NORMAL and UNUSED may be exchanged");
+    changed = true;
+  }
+  if (!changed) return SPM_OK;
+  // Quiesce: the resident small-call servers end (their arguments were
+  // captured at launch; the next small call restarts them with the new
+  // state), then every stream this handle has work on drains.
+  if (!m->host_only) {
+    std::vector<spm_amd::EncodeWorkspace *> all;
+    std::vector<hipStream_t> streams;
+    {
+      std::lock_guard<std::mutex> g(m->pool_mu);
+      for (auto &kv : m->by_stream) {
+        all.push_back(kv.second.get());
+        streams.push_back(kv.first);
+      }
+      for (auto &w : m->host_pool) {
+        all.push_back(w.get());
+        streams.push_back(w->own_stream);
+      }
+    }
+    for (size_t k = 0; k < all.size(); ++k) {
+      std::lock_guard<std::mutex> g(all[k]->mu);
+      all[k]->StopService();
+      std::memset(all[k]->svc_key, 0, sizeof(all[k]->svc_key));
+      SPM_HIP_TRY(hipStreamSynchronize(streams[k]));
+    }
+  }
+  std::vector<uint8_t> kind(n, 0);
+  for (uint64_t i = 0; i < n; ++i) {
+    pieces[i].type = types[i];
+    kind[i] = types[i] == spm_amd::kUserDefined ? spm_amd::kKindUserDefined
+              : types[i] == spm_amd::kUnused    ? spm_amd::kKindUnused
+                                                : 0;
+  }
+  const hipStream_t st = nullptr;
+  if (m->model_type == spm_amd::kUnigram) {
+    const bool had_uvs = m->d_uvs.ptr != nullptr;
+    for (size_t u = 0; u < m->trie.units.size(); ++u) {
+      if (!spm_amd::DoubleArray::Leaf(m->trie.units[u])) continue;
+      const int32_t id = m->trie.values[u] & spm_amd::kIdMask;
+      m->trie.values[u] = id | (static_cast<int32_t>(kind[id]) << spm_amd::kKindShift);
+    }
+    std::vector<float> vbp;
+    DeriveUnigram(m, &vbp);
+    if (m->host_only) return SPM_OK;
+    SPM_HIP_TRY(Upload(&m->d_types_kind, kind));
+    SPM_HIP_TRY(spm_amd::LaunchVocabRetagUnigram(m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                                                 had_uvs ? m->d_uvs.as<uint32_t>() : nullptr,
+                                                 m->d_scores.as<float>(), m->d_types_kind.as<uint8_t>(),
+                                                 static_cast<uint32_t>(m->trie.units.size()),
+                                                 static_cast<uint32_t>(n), st));
+    // A tier that had no (unit, score) table at load and needs one now gets
+    // it built on the host, as at load.
+    int rc = SPM_OK;
+    if (!had_uvs && !vbp.empty()) rc = UploadUnitScores(m, vbp);
+    if (rc == SPM_OK) rc = UploadPieceTable(m);
+    if (rc != SPM_OK) return rc;
+  } else if (m->model_type == spm_amd::kBpe) {
+    if (m->host_only) return SPM_OK;
+    SPM_HIP_TRY(Upload(&m->bpe.piece_kind, kind));
+    SPM_HIP_TRY(spm_amd::LaunchVocabRetagBpe(m->bpe.pair_ent.ptr, m->bpe.pair_mask + 1, m->bpe.piece_kind.as<uint8_t>(),
+                                             static_cast<uint32_t>(n), st));
+  } else {
+    return SPM_OK;  // WORD / CHAR encode does not look at NORMAL against UNUSED
+  }
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  return SPM_OK;
+}
+
+int spm_hip_model_set_vocabulary(spm_hip_model *m, const uint8_t *piece_bytes, const uint64_t *piece_offsets,
+                                 uint64_t num_pieces) {
+  if (!m || (num_pieces && (!piece_bytes || !piece_offsets))) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (m->model_type != spm_amd::kUnigram && m->model_type != spm_amd::kBpe)
+    return Fail(SPM_INTERNAL, "Vocabulary constraint is only enabled in subword units.");
+  std::vector<uint8_t> types(m->proto.pieces.size());
+  for (size_t i = 0; i < types.size(); ++i) types[i] = static_cast<uint8_t>(m->proto.pieces[i].type);
+  std::vector<char> keep(types.size(), 0);
+  for (uint64_t k = 0; k < num_pieces; ++k) {
+    const std::string p(reinterpret_cast<const char *>(piece_bytes) + piece_offsets[k],
+                        piece_offsets[k + 1] - piece_offsets[k]);
+    auto it = m->pieces.find(p);
+    if (it != m->pieces.end()) keep[it->second] = 1;
+    auto r = m->reserved.find(p);
+    if (r != m->reserved.end()) keep[r->second] = 1;
+  }
+  for (size_t i = 0; i < types.size(); ++i) {
+    if (types[i] != spm_amd::kNormal && types[i] != spm_amd::kUnused) continue;
+    const std::string &p = m->proto.pieces[i].piece;
+    // string_util::OneCharLen(piece.c_str()) == piece.size()
+    const bool one_char = spm_amd::OneCharLen(static_cast<uint8_t>(p.c_str()[0])) == p.size();
+    types[i] = keep[i] || one_char ? spm_amd::kNormal : spm_amd::kUnused;
+  }
+  return spm_hip_model_set_piece_types(m, types.data(), types.size());
+}
+
+int spm_hip_model_reset_vocabulary(spm_hip_model *m) {
+  if (!m) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  std::vector<uint8_t> types(m->proto.pieces.size());
+  for (size_t i = 0; i < types.size(); ++i) {
+    types[i] = static_cast<uint8_t>(m->proto.pieces[i].type);
+    if (types[i] == spm_amd::kUnused) types[i] = spm_amd::kNormal;
+  }
+  return spm_hip_model_set_piece_types(m, types.data(), types.size());
+}
+
+// ---- Piece counting ----
+
+int spm_hip_count_ids(spm_hip_model *m, const int32_t *d_ids, uint64_t num_tokens, uint64_t *d_counts,
+                      uint32_t *d_status, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_count_ids");
+  if (!m || !d_counts || (num_tokens && !d_ids)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "host-only model handle");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForStream(m, st));
+  if (!d_status) {
+    SPM_HIP_TRY(ws->w_vstat.Reserve(4));
+    d_status = ws->w_vstat.as<uint32_t>();
+    SPM_HIP_TRY(hipMemsetAsync(d_status, 0, 4, st));
+  }
+  // The LDS bins are 32 bits wide: at most 2^31 tokens per launch.
+  const uint32_t v = static_cast<uint32_t>(m->proto.pieces.size());
+  for (uint64_t at = 0; at < num_tokens; at += 1ull << 31)
+    SPM_HIP_TRY(spm_amd::LaunchVocabCount(d_ids + at, std::min<uint64_t>(num_tokens - at, 1ull << 31), d_counts, v,
+                                          d_status, st));
+  return SPM_OK;
+}
+
+int spm_hip_count_ids_host(spm_hip_model *m, const int32_t *ids, uint64_t num_tokens, uint64_t *counts,
+                           uint32_t *status) {
+  spm_amd::TraceRange trace_range_("spm_hip_count_ids_host");
+  if (!m || !counts || (num_tokens && !ids)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "host-only model handle");
+  const uint64_t v = m->proto.pieces.size();
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForHost(m));
+  hipStream_t st = ws.stream();
+  SPM_HIP_TRY(ws->h_ids.Reserve(std::max<uint64_t>(num_tokens, 1) * sizeof(int32_t)));
+  SPM_HIP_TRY(ws->w_vcount.Reserve(v * sizeof(uint64_t) + 8));
+  uint64_t *d_counts = ws->w_vcount.as<uint64_t>();
+  uint32_t *d_status = reinterpret_cast<uint32_t *>(d_counts + v);
+  if (num_tokens) SPM_HIP_TRY(hipMemcpyAsync(ws->h_ids.ptr, ids, num_tokens * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  if (v) SPM_HIP_TRY(hipMemcpyAsync(d_counts, counts, v * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  SPM_HIP_TRY(hipMemsetAsync(d_status, 0, 8, st));
+  for (uint64_t at = 0; at < num_tokens; at += 1ull << 31)
+    SPM_HIP_TRY(spm_amd::LaunchVocabCount(ws->h_ids.as<int32_t>() + at, std::min<uint64_t>(num_tokens - at, 1ull << 31),
+                                          d_counts, static_cast<uint32_t>(v), d_status, st));
+  if (v) SPM_HIP_TRY(hipMemcpyAsync(counts, d_counts, v * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, d_status, 4, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  if (status) *status = ws->pinned[0];
   return SPM_OK;
 }
 

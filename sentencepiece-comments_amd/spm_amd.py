@@ -51,6 +51,8 @@ EXPORTED = [
     "spm_hip_sample_encode_batch", "spm_hip_sample_encode_batch_host", "spm_hip_sample_uniform",
     "spm_hip_nbest_encode_batch", "spm_hip_nbest_encode_batch_host", "spm_hip_model_set_nbest_max_hyps",
     "spm_hip_nbest_last_stats",
+    "spm_hip_model_set_piece_types", "spm_hip_model_get_piece_types", "spm_hip_model_set_vocabulary",
+    "spm_hip_model_reset_vocabulary", "spm_hip_count_ids", "spm_hip_count_ids_host",
 ]
 
 ABI_VERSION = 3  # SPM_HIP_ABI_VERSION of include/spm_hip.h (struct layouts below)
@@ -234,6 +236,12 @@ def lib():
         L.spm_hip_bpe_refresh_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_float)]
         L.spm_hip_bpe_refresh_free.argtypes = [P]
         L.spm_hip_bpe_refresh_free.restype = None
+        L.spm_hip_model_set_piece_types.argtypes = [P, P, U64]
+        L.spm_hip_model_get_piece_types.argtypes = [P, P, U64]
+        L.spm_hip_model_set_vocabulary.argtypes = [P, P, P, U64]
+        L.spm_hip_model_reset_vocabulary.argtypes = [P]
+        L.spm_hip_count_ids.argtypes = [P, P, U64, P, P, P]
+        L.spm_hip_count_ids_host.argtypes = [P, P, U64, P, ctypes.POINTER(ctypes.c_uint32)]
         _lib = L
     return _lib
 
@@ -329,6 +337,48 @@ class DeviceModel:
             return None
         _check(rc)
         return i.value, s.value
+
+    def piece_types(self):
+        """ModelProto::SentencePiece::Type per piece id (uint8), as the handle holds them now."""
+        t = np.zeros(self.info().piece_size, dtype=np.uint8)
+        _check(self._L.spm_hip_model_get_piece_types(self.h, _p(t), len(t)))
+        return t
+
+    def set_piece_types(self, types):
+        """spm_hip_model_set_piece_types: installs a per-piece type vector on
+        the loaded model, in place (only NORMAL <-> UNUSED changes; the
+        load-time scores, trie and BPE tables stay)."""
+        t = np.ascontiguousarray(types, dtype=np.uint8)
+        _check(self._L.spm_hip_model_set_piece_types(self.h, _p(t), len(t)))
+
+    def set_vocabulary(self, pieces):
+        """SentencePieceProcessor::SetVocabulary over the model's own pieces
+        (spm_hip_model_set_vocabulary): the given pieces and every
+        one-character piece become NORMAL, the rest UNUSED."""
+        buf, off = to_csr([p if isinstance(p, bytes) else p.encode() for p in pieces])
+        _check(self._L.spm_hip_model_set_vocabulary(self.h, _p(buf), _p(off), len(pieces)))
+
+    def reset_vocabulary(self):
+        """SentencePieceProcessor::ResetVocabulary: every UNUSED piece becomes NORMAL."""
+        _check(self._L.spm_hip_model_reset_vocabulary(self.h))
+
+    def count_ids_device(self, d_ids, num_tokens, d_counts, d_status=None, stream=None):
+        """spm_hip_count_ids: d_counts[id] (uint64, piece_size) += occurrences
+        of id in d_ids[0, num_tokens); enqueued on `stream`."""
+        _check(self._L.spm_hip_count_ids(self.h, d_ids, num_tokens, d_counts, d_status, stream))
+
+    def count_ids_host(self, ids, counts=None):
+        """spm_hip_count_ids_host: (counts + occurrences per id, status).
+        status bit 0: an id outside [0, piece_size) was skipped."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        v = self.info().piece_size
+        c = np.zeros(v, dtype=np.uint64) if counts is None else np.ascontiguousarray(counts, dtype=np.uint64).copy()
+        if len(c) != v:
+            raise ValueError("count_ids_host needs one counter per piece")
+        st = ctypes.c_uint32(0)
+        pin = ids if ids.size else np.zeros(1, dtype=np.int32)
+        _check(self._L.spm_hip_count_ids_host(self.h, _p(pin), ids.size, _p(c), ctypes.byref(st)))
+        return c, st.value
 
     def stats(self):
         st = EncodeStats()
