@@ -65,12 +65,16 @@ struct EncodeWorkspace {
   DevBuf w_tids, w_tlen, w_ttok;  // SentencePieceText path: raw ids, piece lengths, token offsets
   DevBuf w_vstat, w_vcount;       // piece counting: status word; the host entry's counters
   DevBuf h_in, h_off, h_ids, h_len, h_tok;  // staging for the host API
-  // Host API small batches (EncodeHostSmall): one device block [control |
-  // offsets | bytes | tok | ids | len] and its pinned host mirror.
+  // Small host calls, one staged image per call (small_layout.h; three
+  // kinds: raw lines, cooperative, lane): pin_small holds the image [offsets
+  // | bytes | tok | ids | len | publication words] and w_small its device
+  // mirror (the lane kind's zeroed control block first).  All small-call
+  // pinned memory is coherent, whichever kind allocated it: the kernels write
+  // into it and the host polls it.
   DevBuf w_small;
   uint8_t *pin_small = nullptr;
   size_t pin_small_cap = 0;
-  uint32_t pub_seq = 0;  // EncodeHostSmall's publication sequence
+  uint32_t pub_seq = 0;  // the small calls' publication sequence, all kinds (30 bits, never 0)
   // Resident small-call server (coop_service_kernel) on its own stream: its
   // box in pinned coherent memory, the arguments it was launched with.
   hipStream_t svc_stream = nullptr;

@@ -28,6 +28,7 @@
 #include "piece_table.h"
 #include "sample_rng.h"
 #include "shard_plan.h"
+#include "small_layout.h"
 #include "trace.h"
 
 namespace {
@@ -580,6 +581,29 @@ uint32_t CoopMinNb(const spm_hip_model *m) {
   return m->coop_min_nb.load();
 }
 
+// SPM_HIP_COOP_PROF (debug): a cooperative kernel's phase cycles to stderr.
+// CoopProfiled runs `launch` with zeroed counters on `st` and waits for it.
+bool CoopProf() {
+  static const bool on = std::getenv("SPM_HIP_COOP_PROF") != nullptr;
+  return on;
+}
+
+template <typename Launch>
+int CoopProfiled(hipStream_t st, Launch launch) {
+  uint64_t *prof = nullptr, h[8];
+  SPM_HIP_TRY(spm_amd::DevMalloc(&prof, 64));
+  SPM_HIP_TRY(hipMemsetAsync(prof, 0, 64, st));
+  SPM_HIP_TRY(launch(prof));
+  SPM_HIP_TRY(hipMemcpyAsync(h, prof, 64, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  (void)spm_amd::DevFree(prof);
+  std::fprintf(stderr, "coop prof: setup %llu lattice %llu viterbi %llu backtrace %llu ids %llu cycles; "
+               "bytes %llu chars %llu tokens %llu\n", (unsigned long long)h[0], (unsigned long long)h[1],
+               (unsigned long long)h[2], (unsigned long long)h[3], (unsigned long long)h[4],
+               (unsigned long long)h[5], (unsigned long long)h[6], (unsigned long long)h[7]);
+  return SPM_OK;
+}
+
 // Work buffers and launch tables; `status` = a zeroed control block of
 // PrepareControl's size (nullptr: PrepareControl zeroes the workspace's).
 int FastSetup(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd::EncodeCall &c, uint32_t *status,
@@ -688,23 +712,14 @@ int FastPartB(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd::Enc
                                                status + spm_amd::kStCoopShort, st));
     }
     const uint64_t blocks = fp->coop_blocks;
-    static const bool kProf = std::getenv("SPM_HIP_COOP_PROF") != nullptr;  // debug: phase cycles to stderr
-    uint64_t *prof = nullptr;
-    if (kProf) {
-      SPM_HIP_TRY(spm_amd::DevMalloc(&prof, 64));
-      SPM_HIP_TRY(hipMemsetAsync(prof, 0, 64, st));
-      ca.prof = prof;
-    }
-    SPM_HIP_TRY(spm_amd::LaunchCoopEncode(ca, static_cast<uint32_t>(blocks), st));
-    if (prof) {
-      uint64_t h[8];
-      SPM_HIP_TRY(hipMemcpyAsync(h, prof, 64, hipMemcpyDeviceToHost, st));
-      SPM_HIP_TRY(hipStreamSynchronize(st));
-      (void)spm_amd::DevFree(prof);
-      std::fprintf(stderr, "coop prof: setup %llu lattice %llu viterbi %llu backtrace %llu ids %llu cycles; "
-                   "bytes %llu chars %llu tokens %llu\n", (unsigned long long)h[0], (unsigned long long)h[1],
-                   (unsigned long long)h[2], (unsigned long long)h[3], (unsigned long long)h[4],
-                   (unsigned long long)h[5], (unsigned long long)h[6], (unsigned long long)h[7]);
+    if (CoopProf()) {
+      const int rc = CoopProfiled(st, [&](uint64_t *prof) {
+        ca.prof = prof;
+        return spm_amd::LaunchCoopEncode(ca, static_cast<uint32_t>(blocks), st);
+      });
+      if (rc != SPM_OK) return rc;
+    } else {
+      SPM_HIP_TRY(spm_amd::LaunchCoopEncode(ca, static_cast<uint32_t>(blocks), st));
     }
     glist = ws->w_crest.as<uint32_t>();
     gcount = status + spm_amd::kStCoopRest;
@@ -1911,30 +1926,6 @@ namespace {
 constexpr uint64_t kSmallMaxSentences = 256;    // one fast-kernel tile
 constexpr uint64_t kSmallMaxBytes = 1ull << 20;  // pinned staging bound
 
-inline uint64_t Align256(uint64_t x) { return (x + 255) & ~255ull; }
-
-// Host API, small batches (one fast-kernel tile: n <= 256; unigram fast
-// kernels; offsets start at 0).  The reference calls Encode once per line
-// (spm_encode_main.cc:189-191, model_interface.h:117); the blocking path
-// costs that four synchronizations, pageable copies and a dozen launches.
-// Here the zeroed control block, the offsets and the bytes go up in ONE copy
-// from pinned staging; the fast kernel's single tile starts at byte 0, so
-// its slots are the final ids / lengths / token offsets (no tile
-// compaction); the status words and the outputs come back with one
-// synchronization.  Only a batch the fast kernel flagged runs the general
-// kernel and the fix-up chain, with a second round trip.  *done = false:
-// the caller takes the general blocking path (a device-path overflow).
-// Host API, very small batches (n <= kCoopSmallMax, unigram models with the
-// cooperative kernel's tables): ONE launch of coop_small_kernel, one block
-// whose waves encode a sentence each (its trie walks 64 at a time, the
-// latency a one-sentence call is made of), with the input read from and the
-// outputs written to pinned host memory and completion polled on a host
-// word.  *done = false: the caller takes the lane-kernel small path.
-// Raw lines -> final ids of Encode(line, &ids) without extra options, in one
-// launch (coop_raw_kernel): the raw image goes up through pinned coherent
-// memory, ids and offsets come back there, the host polls the completion
-// word.  *done = false: a line the fused path does not take (general-kernel
-// lattice, a line past kRawMaxBytes, an output past its capacity).
 // The resident small-call server (coop_service_kernel, CoopServiceBox):
 // on by default; SPM_HIP_SERVICE=0 launches one kernel per call instead.
 // SPM_HIP_SERVICE_IDLE_US: wall-clock microseconds without a request after
@@ -1961,13 +1952,115 @@ uint64_t ServiceIdleTicks() {
   return ticks;
 }
 
+// The pinned image and the device buffers of one small call, of any kind.
+// The server's launch tables point into all of them (svc_key) and a buffer
+// that grows is reallocated, so the server is stopped first whenever one
+// must.  pin_small is always coherent (fine-grained): the kernels read the
+// input image from it and write the outputs and the publication word into it
+// directly, and the host polls that word.
+int ReserveSmall(spm_amd::EncodeWorkspace *ws, const spm_amd::SmallLayout &l) {
+  // The lane kind has no slots: FastSetup reserves its work buffers, nothing of these four.
+  const uint64_t rows = l.slots ? (l.slots + 64) * spm_amd::kCoopSlots : 0;
+  const std::pair<spm_amd::DevBuf *, uint64_t> want[] = {{&ws->w_small, l.dev_bytes},
+                                                         {&ws->w_slot2_ids, l.slots * 4},
+                                                         {&ws->w_slot2_len, l.slot_len_bytes},
+                                                         {&ws->w_cpv, rows * 2},
+                                                         {&ws->w_cnd, rows * 4}};
+  bool grows = ws->pin_small_cap < l.pin_bytes;
+  for (const auto &w : want) grows |= w.first->cap < w.second;
+  if (grows) ws->StopService();
+  for (const auto &w : want) SPM_HIP_TRY(w.first->Reserve(w.second));
+  if (ws->pin_small_cap < l.pin_bytes) {
+    if (ws->pin_small) SPM_HIP_TRY(hipHostFree(ws->pin_small));
+    ws->pin_small = nullptr;
+    ws->pin_small_cap = 0;
+    const size_t want_pin = std::max<uint64_t>(l.pin_bytes, 64 << 10);
+    SPM_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ws->pin_small), want_pin, hipHostMallocCoherent));
+    ws->pin_small_cap = want_pin;
+  }
+  return SPM_OK;
+}
+
+// The call's publication sequence number: 30 bits (the server's request word
+// keeps the call kind above them), never 0 (a cleared publication word).
+uint32_t NextPubSeq(spm_amd::EncodeWorkspace *ws) {
+  if ((++ws->pub_seq & 0x3FFFFFFFu) == 0) ++ws->pub_seq;
+  return ws->pub_seq & 0x3FFFFFFFu;
+}
+
+// What a one-block kernel is told of the staged call: its sizes, the input's
+// place in the image and the outputs' in pinned memory.
+spm_amd::CoopCall SmallCoopCall(spm_amd::EncodeWorkspace *ws, const spm_amd::SmallLayout &l, uint64_t n,
+                                bool with_len) {
+  uint8_t *h = ws->pin_small;
+  spm_amd::CoopCall c{};
+  c.n = static_cast<uint32_t>(n);
+  c.stage_words = l.stage_words();
+  c.pub_seq = NextPubSeq(ws);
+  c.in_at = l.in;
+  c.ids_cap = l.ids_cap;
+  c.tok = l.Tok(h);
+  c.ids = l.Ids(h);
+  c.len = with_len ? l.Len(h) : nullptr;
+  c.host_pub = l.Pub(h);
+  return c;
+}
+
+// Completion: the kernel's publication word, polled until pub[0] == seq; the
+// stream is queried now and then so that a kernel that ended without
+// publishing (an early exit: *published = false) or failed (the stream is
+// synchronized, the HIP error returned) is noticed.
+int WaitPublished(volatile const uint32_t *pub, uint32_t seq, hipStream_t st, bool *published) {
+  *published = false;
+  for (uint32_t spin = 1; pub[0] != seq; ++spin) {
+    if ((spin & 1023) != 0) continue;
+    const hipError_t q = hipStreamQuery(st);
+    if (q == hipSuccess) {
+      if (pub[0] != seq) return SPM_OK;
+      break;
+    }
+    if (q != hipErrorNotReady) {
+      (void)hipStreamSynchronize(st);
+      return Fail(SPM_INTERNAL, std::string("HIP: ") + hipGetErrorString(q));
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  *published = true;
+  return SPM_OK;
+}
+
+// The tail of a normalized small call: tok, then tok[n] ids and lengths out
+// of the pinned image, and the call's stats (slot >= 0: the lane kernels'
+// timed ring slot).
+int FinishSmall(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd::SmallLayout &l, uint64_t n,
+                uint32_t flagged, int slot, int32_t *ids, uint32_t *len, uint64_t *tok) {
+  uint8_t *h = ws->pin_small;
+  std::memcpy(tok, l.Tok(h), (n + 1) * 8);
+  const uint64_t ntok = tok[n];
+  if (ntok) {
+    std::memcpy(ids, l.Ids(h), ntok * 4);
+    if (len) std::memcpy(len, l.Len(h), ntok * 4);
+  }
+  ws->stats = spm_hip_encode_stats{};
+  ws->stats.sentences = n;
+  ws->stats.general_path = flagged;
+  ws->stats.tokens = ntok;
+  if (m->timing && slot >= 0) {
+    SPM_HIP_TRY(hipEventSynchronize(ws->tev[2 * slot + 1]));
+    SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.fast_kernel_ms, ws->tev[2 * slot], ws->tev[2 * slot + 1]));
+    if (flagged) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
+    ws->tcount = 0;
+  }
+  spm_amd::PublishStats(m, ws->stats);
+  return SPM_OK;
+}
+
 // One small call through the server (kind 1: normalized batch with `sa`,
 // 2: raw lines with `ra`), or, with the server off, one launch on `st`; then
-// the poll of host_pub[0] == c.pub_seq.  A server that has exited meanwhile
-// (idle timeout before it saw the request) is relaunched to serve it.
+// the wait for host_pub[0] == c.pub_seq.  A server that has exited meanwhile
+// (idle timeout before it saw the request) is relaunched once to serve it.
 int RunSmallCall(spm_amd::EncodeWorkspace *ws, int kind, const spm_amd::CoopSmallArgs *sa,
                  const spm_amd::CoopRawArgs *ra, const spm_amd::CoopCall &c, hipStream_t st, const char *what) {
-  volatile uint32_t *pub = c.host_pub;
   const bool svc = ServiceOn();
   hipStream_t wait_st = st;
   uint32_t prev = 0;
@@ -2007,73 +2100,37 @@ int RunSmallCall(spm_amd::EncodeWorkspace *ws, int kind, const spm_amd::CoopSmal
   } else {
     SPM_HIP_TRY(spm_amd::LaunchCoopRaw(*ra, c, st));
   }
-  bool published = false, relaunched = false;
-  for (uint32_t spin = 1;; ++spin) {
-    if (pub[0] == c.pub_seq) {
-      published = true;
-      break;
-    }
-    if ((spin & 1023) == 0) {
-      const hipError_t q = hipStreamQuery(wait_st);
-      if (q == hipSuccess) {
-        if (pub[0] == c.pub_seq) {
-          published = true;
-          break;
-        }
-        if (!svc || relaunched) break;
-        // The server exited (idle) before it saw this request: serve it.
-        ws->svc_running = false;
-        relaunched = true;
-        SPM_HIP_TRY(launch(prev));
-        continue;
-      }
-      if (q != hipErrorNotReady) {
-        (void)hipStreamSynchronize(wait_st);
-        ws->svc_running = false;
-        return Fail(SPM_INTERNAL, std::string("HIP: ") + hipGetErrorString(q));
-      }
-    }
+  bool published = false;
+  int rc = WaitPublished(c.host_pub, c.pub_seq, wait_st, &published);
+  if (rc == SPM_OK && !published && svc) {
+    // The server exited (idle) before it saw this request: serve it.
+    ws->svc_running = false;
+    SPM_HIP_TRY(launch(prev));
+    rc = WaitPublished(c.host_pub, c.pub_seq, wait_st, &published);
   }
-  std::atomic_thread_fence(std::memory_order_acquire);
+  if (rc != SPM_OK) {
+    ws->svc_running = false;
+    return rc;
+  }
   if (!published) return Fail(SPM_INTERNAL, std::string(what) + " ended without publishing");
   return SPM_OK;
 }
 
+// Raw lines -> final ids of Encode(line, &ids) without extra options, in one
+// launch (coop_raw_kernel): the raw image goes up through pinned coherent
+// memory, ids and offsets come back there, the host polls the completion
+// word.  *done = false: a line the fused path does not take (general-kernel
+// lattice, a line past kRawMaxBytes, an output past its capacity).
 int EncodeRawCoop(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *raw, const uint64_t *raw_off,
                   uint64_t n, int32_t *ids, uint64_t ids_cap, uint64_t *out_off, hipStream_t st, bool *done) {
   *done = false;
-  const uint64_t total = raw_off[n];
-  const uint64_t ncap = 4 * total + 8 * n + 64;
-  const uint64_t o_raw = Align256((n + 1) * 8), in_end = o_raw + total;
-  const uint64_t o_out = Align256(in_end + 16), o_ids = Align256(o_out + (n + 1) * 8);
-  const uint64_t o_pub = Align256(o_ids + ncap * 4), pin_end = o_pub + 256;
-  // Buffers that grow are reallocated: not under a running server.
-  if (ws->w_small.cap < in_end + 16 || ws->w_slot2_len.cap < ncap || ws->w_slot2_ids.cap < ncap * 4 ||
-      ws->w_cpv.cap < (ncap + 64) * spm_amd::kCoopSlots * 2 || ws->w_cnd.cap < (ncap + 64) * spm_amd::kCoopSlots * 4 ||
-      ws->pin_small_cap < pin_end)
-    ws->StopService();
-  SPM_HIP_TRY(ws->w_small.Reserve(in_end + 16));
-  SPM_HIP_TRY(ws->w_slot2_len.Reserve(ncap));  // normalized bytes
-  SPM_HIP_TRY(ws->w_slot2_ids.Reserve(ncap * 4));
-  SPM_HIP_TRY(ws->w_cpv.Reserve((ncap + 64) * spm_amd::kCoopSlots * 2));
-  SPM_HIP_TRY(ws->w_cnd.Reserve((ncap + 64) * spm_amd::kCoopSlots * 4));
-  if (ws->pin_small_cap < pin_end) {
-    if (ws->pin_small) SPM_HIP_TRY(hipHostFree(ws->pin_small));
-    ws->pin_small = nullptr;
-    ws->pin_small_cap = 0;
-    const size_t want = std::max<uint64_t>(pin_end, 64 << 10);
-    SPM_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ws->pin_small), want, hipHostMallocCoherent));
-    ws->pin_small_cap = want;
-  }
+  const spm_amd::SmallLayout l = spm_amd::MakeSmallLayout(spm_amd::SmallKind::kRaw, n, raw_off[n]);
+  int rc = ReserveSmall(ws, l);
+  if (rc != SPM_OK) return rc;
   uint8_t *h = ws->pin_small;
   uint8_t *d = ws->w_small.as<uint8_t>();
-  std::memcpy(h, raw_off, (n + 1) * 8);
-  if (total) std::memcpy(h + o_raw, raw, total);
-  volatile uint32_t *pub = reinterpret_cast<volatile uint32_t *>(h + o_pub);
-  pub[0] = 0;
-  if ((++ws->pub_seq & 0x3FFFFFFFu) == 0) ++ws->pub_seq;
-  const uint32_t seq = ws->pub_seq & 0x3FFFFFFFu;
-  spm_amd::CoopArgs a{ws->w_slot2_len.as<uint8_t>(), nullptr, m->d_uvs.as<uint32_t>(),
+  l.Stage(h, raw_off, raw, n);
+  spm_amd::CoopArgs a{ws->w_slot2_len.as<uint8_t>(), nullptr, m->d_uvs.as<uint32_t>(),  // normalized bytes
                       m->d_values.as<int32_t>(), static_cast<uint32_t>(m->trie.units.size()), m->up,
                       nullptr, nullptr, 0, ws->w_slot2_ids.as<int32_t>(), nullptr, nullptr, nullptr, nullptr,
                       ws->w_cpv.as<uint16_t>(), ws->w_cnd.as<uint32_t>(),
@@ -2092,269 +2149,115 @@ int EncodeRawCoop(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t 
                           reinterpret_cast<uint32_t *>(d),
                           m->d_types.as<uint8_t>(),
                           static_cast<int32_t>(m->proto.pieces.size())};
-  spm_amd::CoopCall c{};
-  c.n = static_cast<uint32_t>(n);
-  c.stage_words = static_cast<uint32_t>((in_end + 3) / 4);
-  c.pub_seq = seq;
-  c.in_at = o_raw;
-  c.ids_cap = ncap;
-  c.tok = reinterpret_cast<uint64_t *>(h + o_out);
-  c.ids = reinterpret_cast<int32_t *>(h + o_ids);
-  c.host_pub = reinterpret_cast<uint32_t *>(h + o_pub);
-  const int rc = RunSmallCall(ws, 2, nullptr, &ra, c, st, "raw-line encode");
+  const spm_amd::CoopCall c = SmallCoopCall(ws, l, n, false);
+  rc = RunSmallCall(ws, 2, nullptr, &ra, c, st, "raw-line encode");
   if (rc != SPM_OK) return rc;
-  if (pub[1] != 0) {  // not taken
+  if (static_cast<volatile uint32_t *>(c.host_pub)[1] != 0) {  // not taken
     ws->StopService();  // the caller's fallback may share the server's hardware queue
     return SPM_OK;
   }
-  std::memcpy(out_off, h + o_out, (n + 1) * 8);
+  std::memcpy(out_off, l.Tok(h), (n + 1) * 8);
   const uint64_t nt = out_off[n];
   if (nt > ids_cap) return Fail(SPM_RESOURCE_EXHAUSTED, "ids exceed ids_cap");
-  if (nt) std::memcpy(ids, h + o_ids, nt * 4);
+  if (nt) std::memcpy(ids, l.Ids(h), nt * 4);
   *done = true;
   return SPM_OK;
 }
 
+// Host API, very small batches (n <= kCoopSmallMax, unigram models with the
+// cooperative kernel's tables): ONE launch of coop_small_kernel, one block
+// whose waves encode a sentence each (its trie walks 64 at a time, the
+// latency a one-sentence call is made of), with the input read from and the
+// outputs written to pinned host memory and completion polled on a host
+// word.  *done = false: the caller takes the lane-kernel small path.
 int EncodeHostCoop(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *bytes, const uint64_t *off,
                    uint64_t n, int32_t *ids, uint32_t *len, uint64_t *tok, hipStream_t st, bool *done) {
   *done = false;
-  const uint64_t total = off[n], cap = std::max<uint64_t>(total, 1);
-  const uint64_t o_in = Align256((n + 1) * 8), in_end = o_in + total;
-  const uint64_t o_tok = Align256(in_end + 16), o_ids = Align256(o_tok + (n + 1) * 8);
-  const uint64_t o_len = Align256(o_ids + cap * 4);
-  const uint64_t o_pub = Align256(o_len + cap * 4), pin_end = o_pub + 256;
-  // Slots, lengths and scratch rows are indexed by the staged byte offset
-  // (o_in + off[i]); buffers that grow are reallocated: not under a server.
-  const uint64_t slots = in_end + 16;
-  if (ws->w_small.cap < in_end + 16 || ws->w_slot2_ids.cap < slots * 4 || ws->w_slot2_len.cap < slots * 4 ||
-      ws->w_cpv.cap < (slots + 64) * spm_amd::kCoopSlots * 2 ||
-      ws->w_cnd.cap < (slots + 64) * spm_amd::kCoopSlots * 4 || ws->pin_small_cap < pin_end)
-    ws->StopService();
-  SPM_HIP_TRY(ws->w_small.Reserve(in_end + 16));
-  SPM_HIP_TRY(ws->w_slot2_ids.Reserve(slots * 4));
-  SPM_HIP_TRY(ws->w_slot2_len.Reserve(slots * 4));
-  SPM_HIP_TRY(ws->w_cpv.Reserve((slots + 64) * spm_amd::kCoopSlots * 2));
-  SPM_HIP_TRY(ws->w_cnd.Reserve((slots + 64) * spm_amd::kCoopSlots * 4));
-  if (ws->pin_small_cap < pin_end) {
-    if (ws->pin_small) SPM_HIP_TRY(hipHostFree(ws->pin_small));
-    ws->pin_small = nullptr;
-    ws->pin_small_cap = 0;
-    const size_t want = std::max<uint64_t>(pin_end, 64 << 10);
-    SPM_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ws->pin_small), want, hipHostMallocCoherent));
-    ws->pin_small_cap = want;
-  }
+  const spm_amd::SmallLayout l = spm_amd::MakeSmallLayout(spm_amd::SmallKind::kCoop, n, off[n]);
+  int rc = ReserveSmall(ws, l);
+  if (rc != SPM_OK) return rc;
   uint8_t *h = ws->pin_small;
   uint8_t *d = ws->w_small.as<uint8_t>();
-  std::memcpy(h, off, (n + 1) * 8);
-  if (total) std::memcpy(h + o_in, bytes, total);
-  volatile uint32_t *pub = reinterpret_cast<volatile uint32_t *>(h + o_pub);
-  pub[0] = 0;
-  if ((++ws->pub_seq & 0x3FFFFFFFu) == 0) ++ws->pub_seq;
-  const uint32_t seq = ws->pub_seq & 0x3FFFFFFFu;
+  l.Stage(h, off, bytes, n);
   spm_amd::CoopArgs a{d, reinterpret_cast<const uint64_t *>(d), m->d_uvs.as<uint32_t>(),
                       m->d_values.as<int32_t>(), static_cast<uint32_t>(m->trie.units.size()), m->up,
                       nullptr, nullptr, 0, ws->w_slot2_ids.as<int32_t>(), ws->w_slot2_len.as<uint32_t>(),
                       nullptr, nullptr, nullptr, ws->w_cpv.as<uint16_t>(), ws->w_cnd.as<uint32_t>(),
                       static_cast<uint32_t>(std::max(m->max_piece_bytes, 4)), nullptr};
   spm_amd::CoopSmallArgs sa{a, reinterpret_cast<const uint32_t *>(h), reinterpret_cast<uint32_t *>(d)};
-  spm_amd::CoopCall c{};
-  c.n = static_cast<uint32_t>(n);
-  c.stage_words = static_cast<uint32_t>((in_end + 3) / 4);
-  c.pub_seq = seq;
-  c.in_at = o_in;
-  c.tok = reinterpret_cast<uint64_t *>(h + o_tok);
-  c.ids = reinterpret_cast<int32_t *>(h + o_ids);
-  c.len = len ? reinterpret_cast<uint32_t *>(h + o_len) : nullptr;
-  c.host_pub = reinterpret_cast<uint32_t *>(h + o_pub);
-  // SPM_HIP_COOP_PROF (debug): phase cycles of this call to stderr (one
-  // launch on `st`, not through the server).
-  static const bool kProf = std::getenv("SPM_HIP_COOP_PROF") != nullptr;
-  if (kProf) {
-    uint64_t *prof = nullptr;
-    SPM_HIP_TRY(spm_amd::DevMalloc(&prof, 64));
-    SPM_HIP_TRY(hipMemsetAsync(prof, 0, 64, st));
-    spm_amd::CoopSmallArgs sp = sa;
-    sp.a.prof = prof;
-    SPM_HIP_TRY(spm_amd::LaunchCoopSmall(sp, c, st));
-    uint64_t hp[8];
-    SPM_HIP_TRY(hipMemcpyAsync(hp, prof, 64, hipMemcpyDeviceToHost, st));
-    SPM_HIP_TRY(hipStreamSynchronize(st));
-    (void)spm_amd::DevFree(prof);
-    std::fprintf(stderr, "coop prof: setup %llu lattice %llu viterbi %llu backtrace %llu ids %llu cycles; "
-                 "bytes %llu chars %llu tokens %llu\n", (unsigned long long)hp[0], (unsigned long long)hp[1],
-                 (unsigned long long)hp[2], (unsigned long long)hp[3], (unsigned long long)hp[4],
-                 (unsigned long long)hp[5], (unsigned long long)hp[6], (unsigned long long)hp[7]);
-    if (pub[0] != seq) return Fail(SPM_INTERNAL, "cooperative encode ended without publishing");
+  const spm_amd::CoopCall c = SmallCoopCall(ws, l, n, len != nullptr);
+  volatile uint32_t *pub = c.host_pub;
+  if (CoopProf()) {  // this call's phase cycles: one launch on `st`, not through the server
+    rc = CoopProfiled(st, [&](uint64_t *prof) {
+      spm_amd::CoopSmallArgs sp = sa;
+      sp.a.prof = prof;
+      return spm_amd::LaunchCoopSmall(sp, c, st);
+    });
+    if (rc != SPM_OK) return rc;
+    if (pub[0] != c.pub_seq) return Fail(SPM_INTERNAL, "cooperative encode ended without publishing");
   } else {
-    const int rc = RunSmallCall(ws, 1, &sa, nullptr, c, st, "cooperative encode");
+    rc = RunSmallCall(ws, 1, &sa, nullptr, c, st, "cooperative encode");
     if (rc != SPM_OK) return rc;
   }
   if (pub[1] != 0) {  // a sentence it does not take: not done
     ws->StopService();  // the lane-kernel re-run may share the server's hardware queue
     return SPM_OK;
   }
-  std::memcpy(tok, h + o_tok, (n + 1) * 8);
-  const uint64_t ntok = tok[n];
-  if (ntok) {
-    std::memcpy(ids, h + o_ids, ntok * 4);
-    if (len) std::memcpy(len, h + o_len, ntok * 4);
-  }
-  ws->stats = spm_hip_encode_stats{};
-  ws->stats.sentences = n;
-  ws->stats.tokens = ntok;
-  spm_amd::PublishStats(m, ws->stats);
-  *done = true;
-  return SPM_OK;
+  rc = FinishSmall(m, ws, l, n, 0, -1, ids, len, tok);
+  *done = rc == SPM_OK;
+  return rc;
 }
 
-// The round-4 small path (one pinned upload, outputs copied back, stream
-// synchronization): SPM_HIP_SMALL_ZEROCOPY=0 (A/B knob).
-int EncodeHostSmallCopy(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *bytes, const uint64_t *off,
-                    uint64_t n, int32_t *ids, uint32_t *len, uint64_t *tok, hipStream_t st, bool *done) {
-  *done = false;
-  const uint64_t total = off[n];
-  const uint64_t ctl_bytes = spm_amd::kStWords * 4 + 8 * (spm_amd::FastTiles(n) + spm_amd::kScanTiles);
-  const uint64_t o_off = Align256(ctl_bytes), o_in = Align256(o_off + (n + 1) * 8);
-  const uint64_t in_end = o_in + total;
-  const uint64_t o_tok = Align256(in_end + 16), o_ids = Align256(o_tok + (n + 1) * 8);
-  const uint64_t o_len = Align256(o_ids + std::max<uint64_t>(total, 1) * 4);
-  const uint64_t out_end = len ? o_len + std::max<uint64_t>(total, 1) * 4 : o_ids + std::max<uint64_t>(total, 1) * 4;
-  SPM_HIP_TRY(ws->w_small.Reserve(out_end));
-  if (ws->pin_small_cap < out_end) {
-    if (ws->pin_small) SPM_HIP_TRY(hipHostFree(ws->pin_small));
-    ws->pin_small = nullptr;
-    ws->pin_small_cap = 0;
-    const size_t want = std::max<uint64_t>(out_end, 64 << 10);
-    SPM_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ws->pin_small), want));
-    ws->pin_small_cap = want;
-  }
-  uint8_t *h = ws->pin_small;
-  uint8_t *d = ws->w_small.as<uint8_t>();
-  std::memset(h, 0, ctl_bytes);
-  std::memcpy(h + o_off, off, (n + 1) * 8);
-  if (total) std::memcpy(h + o_in, bytes, total);
-  SPM_HIP_TRY(hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, st));
-  spm_amd::EncodeCall c{d + o_in, reinterpret_cast<uint64_t *>(d + o_off), n, total,
-                        reinterpret_cast<int32_t *>(d + o_ids), len ? reinterpret_cast<uint32_t *>(d + o_len) : nullptr,
-                        reinterpret_cast<uint64_t *>(d + o_tok), nullptr, st, false, 0};
-  ws->stats = spm_hip_encode_stats{};
-  FastPlan fp;
-  int rc = FastSetup(m, ws, c, reinterpret_cast<uint32_t *>(d), &fp);
-  if (rc == SPM_OK) rc = FastPartA(m, ws, c, &fp, false);
-  if (rc != SPM_OK) return rc;
-  auto fetch = [&]() -> hipError_t {
-    hipError_t e = hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h + o_tok, d + o_tok, out_end - o_tok, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e;
-  };
-  SPM_HIP_TRY(fetch());
-  const uint32_t *hs = reinterpret_cast<const uint32_t *>(h);
-  const uint32_t flagged = hs[spm_amd::kStFlagged];
-  if (hs[spm_amd::kStError]) return SPM_OK;  // not done: the blocking path
-  if (flagged) {
-    if ((rc = FastPartB(m, ws, c, &fp)) != SPM_OK) return rc;
-    SPM_HIP_TRY(fetch());
-    if (hs[spm_amd::kStError]) return SPM_OK;
-  }
-  std::memcpy(tok, h + o_tok, (n + 1) * 8);
-  const uint64_t ntok = tok[n];
-  if (ntok) {
-    std::memcpy(ids, h + o_ids, ntok * 4);
-    if (len) std::memcpy(len, h + o_len, ntok * 4);
-  }
-  ws->stats.sentences = n;
-  ws->stats.general_path = flagged;
-  ws->stats.tokens = ntok;
-  if (m->timing && fp.slot >= 0) {
-    SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.fast_kernel_ms, ws->tev[2 * fp.slot], ws->tev[2 * fp.slot + 1]));
-    if (flagged) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
-    ws->tcount = 0;
-  }
-  spm_amd::PublishStats(m, ws->stats);
-  *done = true;
-  return SPM_OK;
-}
-
+// Host API, small batches (one fast-kernel tile: n <= 256; unigram fast
+// kernels; offsets start at 0).  The reference calls Encode once per line
+// (spm_encode_main.cc:189-191, model_interface.h:117); the blocking path
+// costs that four synchronizations, pageable copies and a dozen launches.
+// Here the fast kernel's single tile reads the offsets and the bytes straight
+// from the pinned image, zeroes the control block itself, and writes the
+// final ids / lengths / token offsets into the image (its slots are the
+// outputs: one tile whose slots start at byte 0, no tile compaction); the
+// status words come back with the publication word the host polls.  Only a
+// batch the fast kernel flagged runs the general kernel and the fix-up chain,
+// with a second round trip.  *done = false: the caller takes the general
+// blocking path (a device-path overflow).
 int EncodeHostSmall(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *bytes, const uint64_t *off,
                     uint64_t n, int32_t *ids, uint32_t *len, uint64_t *tok, hipStream_t st, bool *done) {
   *done = false;
   const uint64_t total = off[n];
   const uint64_t ctl_bytes = spm_amd::kStWords * 4 + 8 * (spm_amd::FastTiles(n) + spm_amd::kScanTiles);
-  const uint64_t o_off = Align256(ctl_bytes), o_in = Align256(o_off + (n + 1) * 8);
-  const uint64_t in_end = o_in + total;
-  const uint64_t o_tok = Align256(in_end + 16), o_ids = Align256(o_tok + (n + 1) * 8);
-  const uint64_t o_len = Align256(o_ids + std::max<uint64_t>(total, 1) * 4);
-  const uint64_t out_end = len ? o_len + std::max<uint64_t>(total, 1) * 4 : o_ids + std::max<uint64_t>(total, 1) * 4;
-  const uint64_t o_pub = Align256(out_end), pin_end = o_pub + 256;
-  SPM_HIP_TRY(ws->w_small.Reserve(out_end));
-  if (ws->pin_small_cap < pin_end) {
-    if (ws->pin_small) SPM_HIP_TRY(hipHostFree(ws->pin_small));
-    ws->pin_small = nullptr;
-    ws->pin_small_cap = 0;
-    const size_t want = std::max<uint64_t>(pin_end, 64 << 10);
-    // Coherent (fine-grained): the kernel reads the input image from it and
-    // writes the outputs and the publication word into it directly.
-    SPM_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ws->pin_small), want, hipHostMallocCoherent));
-    ws->pin_small_cap = want;
-  }
+  const auto l = spm_amd::MakeSmallLayout(spm_amd::SmallKind::kLane, n, total, len != nullptr, ctl_bytes);
+  int rc = ReserveSmall(ws, l);
+  if (rc != SPM_OK) return rc;
   uint8_t *h = ws->pin_small;
   uint8_t *d = ws->w_small.as<uint8_t>();
-  std::memcpy(h + o_off, off, (n + 1) * 8);
-  if (total) std::memcpy(h + o_in, bytes, total);
-  volatile uint32_t *pub = reinterpret_cast<volatile uint32_t *>(h + o_pub);
-  pub[0] = 0;
-  const uint32_t seq = ++ws->pub_seq == 0 ? ++ws->pub_seq : ws->pub_seq;
-  // The fast kernel's single tile reads the image straight from h and writes
-  // the final ids / lengths / token offsets into h (its slots are the outputs:
-  // one tile whose slots start at byte 0).
-  spm_amd::EncodeCall c{d + o_in, reinterpret_cast<uint64_t *>(d + o_off), n, total,
-                        reinterpret_cast<int32_t *>(h + o_ids), len ? reinterpret_cast<uint32_t *>(h + o_len) : nullptr,
-                        reinterpret_cast<uint64_t *>(h + o_tok), nullptr, st, false, 0};
-  ws->stats = spm_hip_encode_stats{};
+  l.Stage(h, off, bytes, n);
+  volatile uint32_t *pub = l.Pub(h);
+  const uint32_t seq = NextPubSeq(ws);
+  spm_amd::EncodeCall c{l.In(d), l.Off(d), n, total, l.Ids(h), len ? l.Len(h) : nullptr, l.Tok(h), nullptr,
+                        st, false, 0};
   FastPlan fp;
-  int rc = FastSetup(m, ws, c, reinterpret_cast<uint32_t *>(d), &fp);
+  rc = FastSetup(m, ws, c, reinterpret_cast<uint32_t *>(d), &fp);
   if (rc != SPM_OK) return rc;
   fp.l.stage_src = reinterpret_cast<const uint32_t *>(h);
   fp.l.stage_dst = reinterpret_cast<uint32_t *>(d);
-  fp.l.stage_zero = static_cast<uint32_t>(o_off / 4);  // the status block (ctl_bytes <= o_off)
-  fp.l.stage_words = static_cast<uint32_t>((in_end + 3) / 4);
-  fp.l.host_pub = reinterpret_cast<uint32_t *>(h + o_pub);
+  fp.l.stage_zero = l.zero_words();
+  fp.l.stage_words = l.stage_words();
+  fp.l.host_pub = l.Pub(h);
   fp.l.pub_seq = seq;
   rc = FastPartA(m, ws, c, &fp, false);
   if (rc != SPM_OK) {
     (void)hipStreamSynchronize(st);  // nothing may still read h when it is reused
     return rc;
   }
-  // Completion: the kernel's publication word, polled; the stream is
-  // queried now and then so that a kernel that ended without publishing (an
-  // early exit) or failed is noticed.
   bool published = false;
-  for (uint32_t spin = 1;; ++spin) {
-    if (pub[0] == seq) {
-      published = true;
-      break;
-    }
-    if ((spin & 1023) == 0) {
-      const hipError_t q = hipStreamQuery(st);
-      if (q == hipSuccess) {
-        published = pub[0] == seq;
-        break;
-      }
-      if (q != hipErrorNotReady) {
-        (void)hipStreamSynchronize(st);
-        return Fail(SPM_INTERNAL, std::string("HIP: ") + hipGetErrorString(q));
-      }
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
+  if ((rc = WaitPublished(pub, seq, st, &published)) != SPM_OK) return rc;
   uint32_t sw[spm_amd::kStWords];
   if (published) {
     for (int k = 0; k < spm_amd::kStWords; ++k) sw[k] = pub[1 + k];
-  } else {
+  } else {  // the kernel ended early: the status words say why
     SPM_HIP_TRY(hipMemcpy(sw, d, sizeof(sw), hipMemcpyDeviceToHost));
   }
-  uint32_t flagged = sw[spm_amd::kStFlagged];
+  const uint32_t flagged = sw[spm_amd::kStFlagged];
   if (sw[spm_amd::kStError]) {
     SPM_HIP_TRY(hipStreamSynchronize(st));
     return SPM_OK;  // not done: the blocking path
@@ -2366,28 +2269,13 @@ int EncodeHostSmall(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_
       (void)hipStreamSynchronize(st);
       return rc;
     }
-    SPM_HIP_TRY(hipMemcpyAsync(h + o_pub + 128, d, 16, hipMemcpyDeviceToHost, st));
+    SPM_HIP_TRY(hipMemcpyAsync(l.LateStatus(h), d, 16, hipMemcpyDeviceToHost, st));
     SPM_HIP_TRY(hipStreamSynchronize(st));
-    if (reinterpret_cast<const uint32_t *>(h + o_pub + 128)[spm_amd::kStError]) return SPM_OK;
+    if (l.LateStatus(h)[spm_amd::kStError]) return SPM_OK;
   }
-  std::memcpy(tok, h + o_tok, (n + 1) * 8);
-  const uint64_t ntok = tok[n];
-  if (ntok) {
-    std::memcpy(ids, h + o_ids, ntok * 4);
-    if (len) std::memcpy(len, h + o_len, ntok * 4);
-  }
-  ws->stats.sentences = n;
-  ws->stats.general_path = flagged;
-  ws->stats.tokens = ntok;
-  if (m->timing && fp.slot >= 0) {
-    SPM_HIP_TRY(hipEventSynchronize(ws->tev[2 * fp.slot + 1]));
-    SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.fast_kernel_ms, ws->tev[2 * fp.slot], ws->tev[2 * fp.slot + 1]));
-    if (flagged) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
-    ws->tcount = 0;
-  }
-  spm_amd::PublishStats(m, ws->stats);
-  *done = true;
-  return SPM_OK;
+  rc = FinishSmall(m, ws, l, n, flagged, fp.slot, ids, len, tok);
+  *done = rc == SPM_OK;
+  return rc;
 }
 
 // Blocking SampleEncode on a leased workspace: the fast tier over every
@@ -2800,15 +2688,6 @@ int spm_hip_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint
   if (n >= 1 && n <= kSmallMaxSentences && total <= kSmallMaxBytes && m->model_type == spm_amd::kUnigram &&
       m->kernel != spm_amd::UnigramKernel::kGeneralOnly && !NeedsHostSized(m)) {
     bool done = false;
-    static const bool kZeroCopy = [] {
-      const char *e = std::getenv("SPM_HIP_SMALL_ZEROCOPY");
-      return !(e && std::atoi(e) == 0);
-    }();
-    // SPM_HIP_COOP_SMALL=0: one-sentence calls on the lane kernels too (A/B knob).
-    static const bool kCoopSmall = [] {
-      const char *e = std::getenv("SPM_HIP_COOP_SMALL");
-      return !(e && std::atoi(e) == 0);
-    }();
     // A model whose small calls the cooperative kernel keeps handing back
     // (broken UTF-8, > 8 nodes at a position: each costs a second round
     // trip) skips it after 8 rejections in a row, trying again every 64th
@@ -2816,7 +2695,7 @@ int spm_hip_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint
     const uint32_t rejects = m->coop_small_rejects.load(std::memory_order_relaxed);
     const bool try_coop = rejects < 8 || rejects % 64 == 0;
     if (!try_coop) m->coop_small_rejects.fetch_add(1, std::memory_order_relaxed);
-    if (kCoopSmall && try_coop && n <= spm_amd::kCoopSmallMax && m->d_uvs.ptr && m->max_piece_bytes <= 56 &&
+    if (try_coop && n <= spm_amd::kCoopSmallMax && m->d_uvs.ptr && m->max_piece_bytes <= 56 &&
         !m->force_general) {
       const int rc = EncodeHostCoop(m, ws.get(), bytes, off, n, ids, len, tok, st, &done);
       if (rc != SPM_OK) return rc;
@@ -2826,8 +2705,7 @@ int spm_hip_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint
       }
       m->coop_small_rejects.fetch_add(1, std::memory_order_relaxed);
     }
-    const int rc = kZeroCopy ? EncodeHostSmall(m, ws.get(), bytes, off, n, ids, len, tok, st, &done)
-                             : EncodeHostSmallCopy(m, ws.get(), bytes, off, n, ids, len, tok, st, &done);
+    const int rc = EncodeHostSmall(m, ws.get(), bytes, off, n, ids, len, tok, st, &done);
     if (rc != SPM_OK || done) return rc;
   }
   int rc = StageHostBatch(ws.get(), bytes, off, n, total, len != nullptr, st);
