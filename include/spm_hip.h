@@ -398,6 +398,54 @@ int spm_hip_finalize_ids_async(spm_hip_model *model, const char *extra_options, 
                                uint64_t out_capacity, uint64_t *d_out_offsets, uint32_t *d_status,
                                void *stream);
 
+/* Byte fallback (TrainerSpec.byte_fallback, field 35: the model carries 256
+ * pieces "<0x00>" ... "<0xFF>" of type BYTE = 6).  BYTE pieces are reserved
+ * like CONTROL pieces: never matched against text, outside the trie, the BPE
+ * pair tables and min_score / max_score.  A BYTE piece in a model without the
+ * flag, a BYTE piece whose name is no "<0xXX>", and a model with the flag but
+ * without all 256 bytes are load errors, with the sentencepiece package's
+ * messages.  *enabled: the flag.  byte_ids (may be NULL): the id of every
+ * byte's piece, taken from the pieces' names; -1 without byte fallback.
+ * Works on a host-only handle.
+ *
+ * spm_hip_model_set_piece_types, _set_vocabulary and _reset_vocabulary leave
+ * BYTE pieces as they are (get_piece_types reports 6; exchanging BYTE with any
+ * other type is SPM_INVALID_ARGUMENT).  This is this engine's rule. */
+int spm_hip_model_byte_fallback(const spm_hip_model *model, int *enabled, int32_t byte_ids[256]);
+
+/* spm_hip_finalize_ids for a byte-fallback model.  There PopulateSentencePiece
+ * Text does not merge UNKNOWN runs: every UNKNOWN token is replaced by one
+ * BYTE id per byte of its normalized text (consecutive unknown chars expand
+ * separately), and the extra options apply afterwards ("reverse" reverses the
+ * byte ids too).  That needs each token's bytes, so the call takes, besides
+ * the arguments of spm_hip_finalize_ids, the normalized text the tokens came
+ * from (d_norm_bytes, d_norm_offsets[n+1]: the input of spm_hip_encode_batch)
+ * and d_piece_len (the piece lengths spm_hip_encode_batch writes; the tokens
+ * of a sentence cover exactly its bytes).  Capacity: normalized bytes + n *
+ * (number of bos and eos options) ids always suffice.  On a model without
+ * byte fallback the result is that of spm_hip_finalize_ids and the text is
+ * not read; on a byte-fallback model spm_hip_finalize_ids[_async] returns
+ * SPM_INVALID_ARGUMENT and names this call.  spm_hip_encode_spt needs no
+ * sibling: on a byte-fallback model it writes the byte pieces with norm_begin
+ * == norm_end (piece = IdToPiece(id)); all byte pieces of a token but the
+ * last have begin == end == the token's begin, the last one carries the
+ * token's whole surface.  spm_hip_encode_raw_small_host returns
+ * SPM_UNIMPLEMENTED for a byte-fallback model. */
+int spm_hip_finalize_ids_bytes(spm_hip_model *model, const char *extra_options, const int32_t *d_ids,
+                               const uint32_t *d_piece_len, const uint64_t *d_tok_offsets, uint64_t n,
+                               const uint8_t *d_norm_bytes, const uint64_t *d_norm_offsets,
+                               int32_t *d_out_ids, uint64_t out_capacity, uint64_t *d_out_offsets,
+                               uint64_t *total, void *stream);
+
+/* Pure stream version (status-word contract of spm_hip_encode_batch_async; the
+ * output count is in d_out_offsets[n]; ids that do not fit: nothing is written
+ * and *d_status := SPM_RESOURCE_EXHAUSTED). */
+int spm_hip_finalize_ids_bytes_async(spm_hip_model *model, const char *extra_options, const int32_t *d_ids,
+                                     const uint32_t *d_piece_len, const uint64_t *d_tok_offsets, uint64_t n,
+                                     const uint8_t *d_norm_bytes, const uint64_t *d_norm_offsets,
+                                     int32_t *d_out_ids, uint64_t out_capacity, uint64_t *d_out_offsets,
+                                     uint32_t *d_status, void *stream);
+
 /* Batched SentencePieceProcessor::Decode(ids) on the device
  * (sentencepiece_processor.cc:670-733): ids -> text.  DEVICE pointers:
  * d_ids / d_tok_offsets[n+1] as produced by spm_hip_encode_batch or
@@ -411,6 +459,13 @@ int spm_hip_finalize_ids_async(spm_hip_model *model, const char *extra_options, 
  * unless the model sets it), any other id gives its piece with every U+2581
  * replaced by one space, after one leading U+2581 is dropped if the text built
  * so far is empty (so [<s>, U+2581, U+2581, U+2581 ABC] decodes to "ABC").
+ * BYTE ids (byte fallback): a maximal run of consecutive BYTE ids of one
+ * sentence, in final order, is decoded greedily as UTF-8 - a valid sequence
+ * of k bytes (trail bytes 0x80..0xBF, no overlong form, no surrogate, at most
+ * U+10FFFF) gives k - 1 empty surfaces and the char on its last id, a byte
+ * that starts no valid sequence inside the run gives U+FFFD.  Byte surfaces
+ * are never space-converted or stripped, and a non-empty one makes the text
+ * non-empty.  spm_hip_model_decode_bound counts 4 bytes for a BYTE id.
  *
  * Output: d_out_bytes (capacity out_capacity bytes; tokens *
  * spm_hip_model_decode_bound always suffices, tokens counting the bos/eos

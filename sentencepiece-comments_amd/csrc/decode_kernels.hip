@@ -30,66 +30,21 @@
 //   fill pass  : out_off of empty sentences and out_off[n]; sets
 //                RESOURCE_EXHAUSTED.
 //
+// A BYTE token (byte fallback) has no table surface: every pass computes it
+// from the token's byte and up to 3 neighbours on each side of its run
+// (ByteTokSurface; the rule and why 3 suffice: decode.h, ByteRunSurface).  Its
+// surface is never stripped, and a non-empty one ends the bos state.
+//
 // No pass reads the table or writes once the call's status word is non-zero.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "decode.h"
+#include "token_tiles.h"
 
 namespace spm_amd {
 namespace {
-
-struct TokView {
-  const int32_t *ids;
-  const uint64_t *tok_off;
-  uint64_t n;
-  uint64_t base;  // tok_off[0], read by each kernel (the id CSR need not start at 0)
-  uint32_t extras;
-};
-
-__device__ __forceinline__ uint64_t SentStart(const TokView &v, uint64_t i) {
-  return v.tok_off[i] - v.base + i * v.extras;
-}
-
-// Largest a in [lo, hi) with S(a) <= g; the caller guarantees S(lo) <= g and
-// (hi == limit or S(hi) > g).  Gallops from lo, so a thread that walks
-// ascending tokens pays for the distance moved.
-__device__ __forceinline__ uint64_t FindSentence(const TokView &v, uint64_t lo, uint64_t limit, uint64_t g) {
-  uint64_t a = lo, b, step = 1;
-  for (;;) {
-    b = a + step;
-    if (b >= limit) {
-      b = limit;
-      break;
-    }
-    if (SentStart(v, b) > g) break;
-    a = b;
-    step <<= 1;
-  }
-  while (b - a > 1) {
-    const uint64_t mid = a + (b - a) / 2;
-    if (SentStart(v, mid) <= g) a = mid;
-    else b = mid;
-  }
-  return a;
-}
-
-struct Range {
-  uint64_t begin, end;
-};
-
-__device__ __forceinline__ Range BlockRange(const TokView &v) {
-  const uint64_t total = SentStart(v, v.n);
-  uint64_t chunk = (total + gridDim.x - 1) / gridDim.x;
-  chunk = (chunk + kDecodeTile - 1) / kDecodeTile * kDecodeTile;
-  Range r;
-  r.begin = static_cast<uint64_t>(blockIdx.x) * chunk;
-  r.end = r.begin + chunk;
-  if (r.begin > total) r.begin = total;
-  if (r.end > total) r.end = total;
-  return r;
-}
 
 struct Tok {
   uint64_t sent;
@@ -129,6 +84,37 @@ __device__ __forceinline__ uint32_t EffLen(uint32_t meta, uint64_t pos, uint32_t
   return (meta >> 1) - (pos == first ? (meta & 1u) : 0u);
 }
 
+// Surface of the BYTE token t (meta mt) at token g: its length, the bytes
+// packed little-endian in *lit.  Reads up to 3 tokens on each side, inside the
+// sentence and the run (decode.h, ByteRunSurface).
+__device__ __forceinline__ uint32_t ByteTokSurface(const TokView &v, const EpilogueExtras &x,
+                                                   const uint32_t *__restrict__ meta, int32_t num_pieces,
+                                                   const Tok &t, uint64_t g, uint32_t mt, uint32_t *lit) {
+  const uint64_t count = SentStart(v, t.sent + 1) - SentStart(v, t.sent);
+  uint8_t w[7] = {0, 0, 0, static_cast<uint8_t>(mt), 0, 0, 0};
+  uint32_t lo = 0, hi = 0;
+  while (lo < 3 && t.pos > lo) {
+    const uint32_t nm = MetaOf(meta, num_pieces, TokenAt(v, x, t.sent, g - lo - 1).id);
+    if (!(nm & kDecodeByteFlag)) break;
+    ++lo;
+    w[3 - lo] = static_cast<uint8_t>(nm);
+  }
+  while (hi < 3 && t.pos + hi + 1 < count) {
+    const uint32_t nm = MetaOf(meta, num_pieces, TokenAt(v, x, t.sent, g + hi + 1).id);
+    if (!(nm & kDecodeByteFlag)) break;
+    ++hi;
+    w[3 + hi] = static_cast<uint8_t>(nm);
+  }
+  uint8_t o[4] = {0, 0, 0, 0};
+  const uint32_t len = ByteRunSurface(w, lo, hi, o);
+  *lit = o[0] | (static_cast<uint32_t>(o[1]) << 8) | (static_cast<uint32_t>(o[2]) << 16) |
+         (static_cast<uint32_t>(o[3]) << 24);
+  return len;
+}
+
+// kB: the model has BYTE pieces (byte fallback).  Without them every pass is
+// the table lookup alone.
+template <bool kB>
 __global__ __launch_bounds__(256) void decode_first_kernel(TokView v, EpilogueExtras x,
                                                            const uint32_t *__restrict__ meta, int32_t num_pieces,
                                                            uint32_t *__restrict__ first, uint64_t *__restrict__ ctl,
@@ -154,7 +140,12 @@ __global__ __launch_bounds__(256) void decode_first_kernel(TokView v, EpilogueEx
         atomicMin(reinterpret_cast<unsigned long long *>(ctl + kDcBadKey), static_cast<unsigned long long>(t.src));
       } else {
         const uint32_t mt = meta[t.id];
-        ne = (mt >> 1) > (mt & 1u);
+        if (kB && (mt & kDecodeByteFlag)) {
+          uint32_t lit;
+          ne = ByteTokSurface(v, x, meta, num_pieces, t, g, mt, &lit) != 0;
+        } else {
+          ne = (mt >> 1) > (mt & 1u);
+        }
       }
     }
     // One atomic per (wave, sentence): the lowest lane of the sentence with a
@@ -170,20 +161,7 @@ __global__ __launch_bounds__(256) void decode_first_kernel(TokView v, EpilogueEx
   }
 }
 
-__device__ __forceinline__ uint64_t BlockSum64(uint64_t v, uint64_t *s_w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), o);
-    const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), o);
-    v += (static_cast<uint64_t>(hi) << 32) | lo;
-  }
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const uint64_t r = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-  __syncthreads();
-  return r;
-}
-
+template <bool kB>
 __global__ __launch_bounds__(256) void decode_count_kernel(TokView v, EpilogueExtras x,
                                                            const uint32_t *__restrict__ meta, int32_t num_pieces,
                                                            const uint32_t *__restrict__ first,
@@ -199,35 +177,19 @@ __global__ __launch_bounds__(256) void decode_count_kernel(TokView v, EpilogueEx
     sent = FindSentence(v, have ? sent : 0, v.n, g);
     have = true;
     const Tok t = TokenAt(v, x, sent, g);
-    sum += EffLen(MetaOf(meta, num_pieces, t.id), t.pos, first[sent]);
+    const uint32_t mt = MetaOf(meta, num_pieces, t.id);
+    if (kB && (mt & kDecodeByteFlag)) {
+      uint32_t lit;
+      sum += ByteTokSurface(v, x, meta, num_pieces, t, g, mt, &lit);
+    } else {
+      sum += EffLen(mt, t.pos, first[sent]);
+    }
   }
   sum = BlockSum64(sum, s_w);
   if (threadIdx.x == 0) block_sum[blockIdx.x] = sum;
 }
 
-// Exclusive scan of one value per thread over the block; *total = the sum.
-__device__ __forceinline__ uint32_t BlockExclusiveScan(uint32_t v, uint32_t *s_w, uint32_t *total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) s_w[w] = inc;
-  __syncthreads();
-  uint32_t before = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t wv = s_w[k];
-    if (k < w) before += wv;
-    tot += wv;
-  }
-  __syncthreads();
-  *total = tot;
-  return before + inc - v;
-}
-
+template <bool kB>
 __global__ __launch_bounds__(256) void decode_write_kernel(TokView v, EpilogueExtras x,
                                                            const uint32_t *__restrict__ meta,
                                                            const uint32_t *__restrict__ off,
@@ -242,6 +204,7 @@ __global__ __launch_bounds__(256) void decode_write_kernel(TokView v, EpilogueEx
   __shared__ uint32_t s_w[4];
   __shared__ uint32_t s_start[kDecodeSubTile];
   __shared__ uint32_t s_src[kDecodeSubTile];
+  __shared__ uint32_t s_lit[kB ? kDecodeSubTile : 1];  // a BYTE token's surface, s_src = kDecodeByteFlag
   if (*chain) return;
   v.base = v.tok_off[0];
   uint64_t before = 0, all = 0;
@@ -261,7 +224,7 @@ __global__ __launch_bounds__(256) void decode_write_kernel(TokView v, EpilogueEx
   for (uint64_t s = r.begin; s < r.end; s += kDecodeSubTile) {
     const uint64_t g = s + threadIdx.x;
     const bool valid = g < r.end;
-    uint32_t len = 0, src = 0;
+    uint32_t len = 0, src = 0, lit = 0;
     uint64_t pos = 1;
     if (valid) {
       sent = FindSentence(v, have ? sent : 0, v.n, g);
@@ -270,8 +233,13 @@ __global__ __launch_bounds__(256) void decode_write_kernel(TokView v, EpilogueEx
       const uint32_t mt = MetaOf(meta, num_pieces, t.id);
       const uint32_t f = first[sent];
       pos = t.pos;
-      len = EffLen(mt, pos, f);
-      if (len) src = off[t.id] + (pos == f ? (mt & 1u) : 0u);
+      if (kB && (mt & kDecodeByteFlag)) {
+        len = ByteTokSurface(v, x, meta, num_pieces, t, g, mt, &lit);
+        src = kDecodeByteFlag;
+      } else {
+        len = EffLen(mt, pos, f);
+        if (len) src = off[t.id] + (pos == f ? (mt & 1u) : 0u);
+      }
     }
     uint32_t sub_total;
     const uint32_t excl = BlockExclusiveScan(len, s_w, &sub_total);
@@ -283,6 +251,7 @@ __global__ __launch_bounds__(256) void decode_write_kernel(TokView v, EpilogueEx
     if (write) {
       s_start[threadIdx.x] = excl;
       s_src[threadIdx.x] = src;
+      if (kB) s_lit[threadIdx.x] = lit;
       __syncthreads();
       for (uint32_t o = threadIdx.x; o < sub_total; o += kDecodeSubTile) {
         // The token holding byte o: the last one that starts at or before o
@@ -293,7 +262,9 @@ __global__ __launch_bounds__(256) void decode_write_kernel(TokView v, EpilogueEx
           if (s_start[mid] <= o) a = mid;
           else b = mid;
         }
-        out[run + o] = bytes[s_src[a] + (o - s_start[a])];
+        const uint32_t from = s_src[a], at = o - s_start[a];
+        if (kB && (from & kDecodeByteFlag)) out[run + o] = static_cast<uint8_t>(s_lit[a] >> (8 * at));
+        else out[run + o] = bytes[from + at];
       }
       __syncthreads();
     }
@@ -366,11 +337,23 @@ hipError_t LaunchDecode(const DecodeLaunch &a, bool resolve_bad, hipStream_t st)
   if (a.n == 0) return hipSuccess;
   TokView v{a.ids, a.tok_off, a.n, 0, a.x.num_pre + a.x.num_post};
   const dim3 grid(kDecodeBlocks), block(kDecodeSubTile);
-  hipLaunchKernelGGL(decode_first_kernel, grid, block, 0, st, v, a.x, a.meta, a.num_pieces, a.first, a.ctl, a.chain);
-  hipLaunchKernelGGL(decode_count_kernel, grid, block, 0, st, v, a.x, a.meta, a.num_pieces, a.first, a.block_sum,
-                     a.chain);
-  hipLaunchKernelGGL(decode_write_kernel, grid, block, 0, st, v, a.x, a.meta, a.off, a.bytes, a.num_pieces, a.first,
-                     a.block_sum, a.ctl, a.out, a.capacity, a.out_off, a.out ? a.piece_begin : nullptr, a.chain);
+  if (a.has_bytes) {
+    hipLaunchKernelGGL(decode_first_kernel<true>, grid, block, 0, st, v, a.x, a.meta, a.num_pieces, a.first, a.ctl,
+                       a.chain);
+    hipLaunchKernelGGL(decode_count_kernel<true>, grid, block, 0, st, v, a.x, a.meta, a.num_pieces, a.first,
+                       a.block_sum, a.chain);
+    hipLaunchKernelGGL(decode_write_kernel<true>, grid, block, 0, st, v, a.x, a.meta, a.off, a.bytes, a.num_pieces,
+                       a.first, a.block_sum, a.ctl, a.out, a.capacity, a.out_off, a.out ? a.piece_begin : nullptr,
+                       a.chain);
+  } else {
+    hipLaunchKernelGGL(decode_first_kernel<false>, grid, block, 0, st, v, a.x, a.meta, a.num_pieces, a.first, a.ctl,
+                       a.chain);
+    hipLaunchKernelGGL(decode_count_kernel<false>, grid, block, 0, st, v, a.x, a.meta, a.num_pieces, a.first,
+                       a.block_sum, a.chain);
+    hipLaunchKernelGGL(decode_write_kernel<false>, grid, block, 0, st, v, a.x, a.meta, a.off, a.bytes, a.num_pieces,
+                       a.first, a.block_sum, a.ctl, a.out, a.capacity, a.out_off, a.out ? a.piece_begin : nullptr,
+                       a.chain);
+  }
   if (a.out && a.piece_begin)
     hipLaunchKernelGGL(decode_begin_kernel, grid, block, 0, st, v, a.ctl, a.capacity, a.out_off, a.piece_begin,
                        a.chain);

@@ -59,6 +59,7 @@ struct EncodeWorkspace {
   // Decode: first non-empty position per sentence, block sums, control words;
   // staging of the host entry (ids, token offsets, text, offsets, begins).
   DevBuf w_dfirst, w_dsum, w_dctl, h_dids, h_dtok, h_dout, h_doff, h_dbegin;
+  DevBuf w_bfsum, w_bfctl;  // byte-fallback epilogue: block sums; output count and status word
   // WORD / CHAR encode: marks per tile, first mark and first sentence of each
   // tile, first mark after each tile
   DevBuf w_wc_count, w_wc_first, w_wc_sent, w_wc_next;
@@ -143,6 +144,11 @@ struct spm_hip_model {
   spm_amd::ModelProtoView proto;
   int32_t model_type = 1;
   int32_t unk_id = -1;
+  // Byte fallback (TrainerSpec.byte_fallback): the id of every byte's BYTE
+  // piece, -1 without it.  d_byte_ids: the device copy (EnsureTypes).
+  bool byte_fallback = false;
+  int32_t byte_ids[256];
+  spm_amd::DevBuf d_byte_ids;
   int32_t max_piece_chars = 0;
   int32_t max_piece_bytes = 0;  // longest non-UNUSED piece (C-string bytes)
   float min_score = 0.f, max_score = 0.f;

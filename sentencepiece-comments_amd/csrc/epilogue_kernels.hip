@@ -11,6 +11,7 @@
 // option list into (pre ids, reversed flag, post ids); every sentence's output
 // is  pre · (merged tokens, reversed if flagged) · post.  Two passes, one
 // sentence per lane: COUNT (merged tokens + extras) → scan → WRITE.
+// (Byte-fallback models do not merge: byte_epilogue_kernels.hip.)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

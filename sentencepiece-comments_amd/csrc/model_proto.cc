@@ -97,7 +97,7 @@ bool ParsePieceRec(const uint8_t *b, size_t n, PieceRec *out) {
       if (w.Fixed32(&bits)) std::memcpy(&out->score, &bits, 4);
     } else if (f == 3 && wt == 0) {
       uint64_t t;
-      if (w.Varint(&t) && t >= kNormal && t <= kUnused) out->type = static_cast<int32_t>(t);
+      if (w.Varint(&t) && t >= kNormal && t <= kBytePiece) out->type = static_cast<int32_t>(t);
     } else {
       w.Skip(wt);
     }
@@ -114,6 +114,8 @@ bool ParseTrainerSpec(const uint8_t *b, size_t n, TrainerSpecView *ts) {
       if (w.Varint(&t) && t >= kUnigram && t <= kChar) ts->model_type = static_cast<int32_t>(t);
     } else if (f == 24 && wt == 0) {
       w.Bool(&ts->treat_whitespace_as_suffix);
+    } else if (f == 35 && wt == 0) {
+      w.Bool(&ts->byte_fallback);
     } else if (f == 44 && wt == 2) {
       ts->has_unk_surface = w.String(&ts->unk_surface);
     } else if (f == 45 && wt == 2) {

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "decode.h"
 #include "scratch_cache.h"
 
 #include <algorithm>
@@ -70,6 +71,7 @@ Status SentencePieceProcessor::LoadImpl(const std::string &serialized, bool host
   proto_ = ModelProtoView();
   pieces_.clear();
   reserved_.clear();
+  std::fill(byte_ids_, byte_ids_ + 256, -1);
   std::string err;
   if (!ParseModelProto(reinterpret_cast<const uint8_t *>(serialized.data()), serialized.size(),
                        &proto_, &err))
@@ -81,6 +83,7 @@ Status SentencePieceProcessor::LoadImpl(const std::string &serialized, bool host
     const auto &p = proto_.pieces[i];
     const bool normal = p.type == kNormal || p.type == kUserDefined || p.type == kUnused;
     (normal ? pieces_ : reserved_).emplace(p.piece, static_cast<int>(i));
+    if (p.type == kBytePiece && PieceToByte(p.piece) >= 0) byte_ids_[PieceToByte(p.piece)] = static_cast<int>(i);
   }
   status_ = Status::Ok();
   // Self-test samples (sentencepiece_processor.cc:135-153).
@@ -125,6 +128,9 @@ bool SentencePieceProcessor::IsUnknown(int id) const {
 }
 bool SentencePieceProcessor::IsControl(int id) const {
   return id >= 0 && id < GetPieceSize() && proto_.pieces[id].type == kControl;
+}
+bool SentencePieceProcessor::IsByte(int id) const {
+  return id >= 0 && id < GetPieceSize() && proto_.pieces[id].type == kBytePiece;
 }
 bool SentencePieceProcessor::IsUnused(int id) const {
   return id >= 0 && id < GetPieceSize() && proto_.pieces[id].type == kUnused;
@@ -216,8 +222,10 @@ Status SentencePieceProcessor::EncodeIdsSmall(const std::vector<std::string> &in
   const uint64_t n = inputs.size();
   uint64_t raw = 0;
   for (const auto &s : inputs) raw += s.size();
+  const bool bf = proto_.trainer_spec.byte_fallback;
   if (extra_.empty() && n <= 16) {
     // One launch: normalize + encode + unknown-run merge (coop_raw_kernel).
+    // (A byte-fallback model gets SPM_UNIMPLEMENTED and takes the chain below.)
     std::vector<uint64_t> roff(n + 1, 0);
     std::string rb;
     rb.reserve(raw);
@@ -244,7 +252,9 @@ Status SentencePieceProcessor::EncodeIdsSmall(const std::vector<std::string> &in
   // ids | tok] (device only) [out_off | out ids] (downloaded).
   const uint64_t o_inoff = 256, o_in = Al256(o_inoff + (n + 1) * 8), up_end = o_in + raw;
   const uint64_t o_norm = Al256(up_end + 16), o_noff = Al256(o_norm + cap_norm);
-  const uint64_t o_ids = Al256(o_noff + (n + 1) * 8), o_tok = Al256(o_ids + cap_norm * 4);
+  // (byte fallback: the piece lengths follow the ids, for spm_hip_finalize_ids_bytes_async)
+  const uint64_t o_ids = Al256(o_noff + (n + 1) * 8), o_len = Al256(o_ids + cap_norm * 4);
+  const uint64_t o_tok = bf ? Al256(o_len + cap_norm * 4) : o_len;
   const uint64_t o_oo = Al256(o_tok + (n + 1) * 8), o_out = Al256(o_oo + (n + 1) * 8);
   const uint64_t end = o_out + cap_out * 4;
   enum { kSmallBlock = 9 };
@@ -281,9 +291,17 @@ Status SentencePieceProcessor::EncodeIdsSmall(const std::vector<std::string> &in
                                                 nullptr, d_status, st);
   if (rc == SPM_OK)
     rc = spm_hip_encode_batch_async(model_, d + o_norm, reinterpret_cast<uint64_t *>(d + o_noff), n, cap_norm,
-                                    reinterpret_cast<int32_t *>(d + o_ids), nullptr,
+                                    reinterpret_cast<int32_t *>(d + o_ids),
+                                    bf ? reinterpret_cast<uint32_t *>(d + o_len) : nullptr,
                                     reinterpret_cast<uint64_t *>(d + o_tok), d_status, st);
-  if (rc == SPM_OK)
+  if (rc == SPM_OK && bf)
+    rc = spm_hip_finalize_ids_bytes_async(model_, extra_str_.c_str(), reinterpret_cast<int32_t *>(d + o_ids),
+                                          reinterpret_cast<uint32_t *>(d + o_len),
+                                          reinterpret_cast<uint64_t *>(d + o_tok), n, d + o_norm,
+                                          reinterpret_cast<uint64_t *>(d + o_noff),
+                                          reinterpret_cast<int32_t *>(d + o_out), cap_out,
+                                          reinterpret_cast<uint64_t *>(d + o_oo), d_status, st);
+  else if (rc == SPM_OK)
     rc = spm_hip_finalize_ids_async(model_, extra_str_.c_str(), reinterpret_cast<int32_t *>(d + o_ids),
                                     reinterpret_cast<uint64_t *>(d + o_tok), n, reinterpret_cast<int32_t *>(d + o_out),
                                     cap_out, reinterpret_cast<uint64_t *>(d + o_oo), d_status, st);
@@ -414,6 +432,9 @@ Status SentencePieceProcessor::DeviceFinalize(const DeviceBatch &b, uint64_t n, 
   *d_out_off = static_cast<uint64_t *>(dev_.Get(kOutOff, (n + 1) * 8));
   *d_out = static_cast<int32_t *>(dev_.Get(kOut, std::max<uint64_t>(cap, 1) * 4));
   if (!*d_out_off || !*d_out) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+  if (proto_.trainer_spec.byte_fallback)  // unknown tokens expand to their bytes: at most b.total ids
+    return FromC(spm_hip_finalize_ids_bytes(model_, extra_str_.c_str(), b.d_ids, b.d_len, b.d_tok, n, b.d_norm,
+                                            b.d_norm_off, *d_out, cap, *d_out_off, fin, nullptr));
   return FromC(spm_hip_finalize_ids(model_, extra_str_.c_str(), b.d_ids, b.d_tok, n, *d_out, cap, *d_out_off, fin,
                                     nullptr));
 }
@@ -475,16 +496,17 @@ Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, 
   const uint64_t ntok = tok_off[n];
   std::vector<int32_t> tok_ids(std::max<uint64_t>(ntok, 1));
   std::vector<uint32_t> tok_len(std::max<uint64_t>(ntok, 1));
-  std::vector<uint8_t> norm(pieces ? std::max<uint64_t>(total, 1) : 0);
+  const bool need_norm = pieces || proto_.trainer_spec.byte_fallback;  // byte pieces come from the text
+  std::vector<uint8_t> norm(need_norm ? std::max<uint64_t>(total, 1) : 0);
   if ((he = hipMemcpy(tok_ids.data(), d_ids, ntok * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
       (he = hipMemcpy(tok_len.data(), d_len, ntok * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
-      (pieces && (he = hipMemcpy(norm.data(), d_norm, total, hipMemcpyDeviceToHost)) != hipSuccess))
+      (need_norm && (he = hipMemcpy(norm.data(), d_norm, total, hipMemcpyDeviceToHost)) != hipSuccess))
     return fail_hip(he);
   if (ids) ids->assign(n, {});
   if (pieces) pieces->assign(n, {});
   std::vector<std::pair<std::string, int>> spt;
   for (uint64_t i = 0; i < n; ++i) {
-    const char *normalized = pieces ? reinterpret_cast<const char *>(norm.data()) + norm_off[i] : nullptr;
+    const char *normalized = need_norm ? reinterpret_cast<const char *>(norm.data()) + norm_off[i] : nullptr;
     Status ps = PopulateText(normalized, norm_off[i + 1] - norm_off[i], tok_ids.data() + tok_off[i],
                              tok_len.data() + tok_off[i], tok_off[i + 1] - tok_off[i], &spt);
     if (!ps.ok()) return ps;
@@ -594,7 +616,8 @@ Status SentencePieceProcessor::CountPieces(const std::vector<std::string> &input
 
 // PopulateSentencePieceText (sentencepiece_processor.cc:488-551) +
 // ApplyExtraOptions (:945-979) over one path's model-level tokens: (piece,
-// id) pairs with unknown runs merged.  normalized == nullptr: ids only.
+// id) pairs with unknown runs merged (byte fallback: expanded to BYTE pieces,
+// which needs the text).  normalized == nullptr: ids only.
 Status SentencePieceProcessor::PopulateText(const char *normalized, uint64_t nlen, const int32_t *tok_ids,
                                             const uint32_t *tok_len, uint64_t count,
                                             std::vector<std::pair<std::string, int>> *out) const {
@@ -610,6 +633,13 @@ Status SentencePieceProcessor::PopulateText(const char *normalized, uint64_t nle
     const bool is_unk = IsUnknown(id);
     if (IsControl(id)) {
       spt.emplace_back(std::move(w), id);
+    } else if (is_unk && proto_.trainer_spec.byte_fallback) {
+      // One BYTE piece per byte of the token, no merge with its neighbours.
+      for (const char c : w) {
+        const int bid = byte_ids_[static_cast<uint8_t>(c)];
+        spt.emplace_back(IdToPiece(bid), bid);
+      }
+      consumed += len;
     } else {
       if (prev_unk && is_unk) spt.back().first += w;
       else spt.emplace_back(std::move(w), id);
@@ -712,7 +742,9 @@ Status SentencePieceProcessor::NBestEncodeBatch(const std::vector<std::string> &
       if (P && (he = hipMemcpy(sc.data(), d_scores, P * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(he);
       for (uint64_t i = 0; i < n; ++i) (*scores)[c0 + i].assign(sc.begin() + path_off[i], sc.begin() + path_off[i + 1]);
     }
-    if (!pieces) {
+    // (Byte fallback expands a path's unknown tokens from the line's text: its
+    // ids come from the host epilogue below, like the pieces.)
+    if (!pieces && !(ids && proto_.trainer_spec.byte_fallback)) {
       if (ids) {
         uint64_t n_extra = 0;
         for (ExtraOption opt : extra_) n_extra += opt != REVERSE;
@@ -756,6 +788,7 @@ Status SentencePieceProcessor::NBestEncodeBatch(const std::vector<std::string> &
           (*ids)[c0 + i].emplace_back();
           for (auto &q : spt) (*ids)[c0 + i].back().push_back(q.second);
         }
+        if (!pieces) continue;
         (*pieces)[c0 + i].emplace_back();
         for (auto &q : spt) (*pieces)[c0 + i].back().push_back(std::move(q.first));
       }
@@ -832,11 +865,26 @@ void SentencePieceProcessor::DecodeLineHost(std::vector<std::pair<std::string, i
   if (!text) return;  // options only
   text->clear();
   std::string surface;
-  for (const auto &pi : *row) {
+  for (size_t at = 0; at < row->size(); ++at) {
+    const auto &pi = (*row)[at];
     const std::string &piece = pi.first;
     const int id = pi.second;
     surface.clear();
     if (IsControl(id)) {
+    } else if (IsByte(id)) {
+      // The byte run around the token, at most 3 tokens each way (decode.h).
+      uint8_t w[7] = {}, lit[4];
+      w[3] = static_cast<uint8_t>(PieceToByte(IdToPiece(id)));
+      uint32_t lo = 0, hi = 0;
+      while (lo < 3 && at > lo && IsByte((*row)[at - lo - 1].second)) {
+        ++lo;
+        w[3 - lo] = static_cast<uint8_t>(PieceToByte(IdToPiece((*row)[at - lo].second)));
+      }
+      while (hi < 3 && at + hi + 1 < row->size() && IsByte((*row)[at + hi + 1].second)) {
+        ++hi;
+        w[3 + hi] = static_cast<uint8_t>(PieceToByte(IdToPiece((*row)[at + hi].second)));
+      }
+      surface.assign(reinterpret_cast<const char *>(lit), ByteRunSurface(w, lo, hi, lit));
     } else if (IsUnknown(id)) {
       surface = IdToPiece(id) == piece ? ts.unk_surface : piece;
     } else {

@@ -158,6 +158,11 @@ class SentencePieceProcessor {
   float GetScore(int id) const;
   bool IsUnknown(int id) const;
   bool IsControl(int id) const;
+  // A BYTE piece ("<0x00>" ... "<0xFF>") of a model trained with
+  // byte_fallback.  Under byte fallback Encode replaces every unknown token by
+  // the BYTE pieces of its bytes instead of <unk>, and Decode turns runs of
+  // BYTE pieces back into text (invalid UTF-8 gives U+FFFD per byte).
+  bool IsByte(int id) const;
   bool IsUnused(int id) const;
   int unk_id() const;
   int bos_id() const;
@@ -169,6 +174,7 @@ class SentencePieceProcessor {
   spm_hip_model *model_ = nullptr;
   ModelProtoView proto_;
   std::unordered_map<std::string, int> pieces_, reserved_;
+  int byte_ids_[256];  // byte fallback: byte -> id of its BYTE piece (-1 without)
   std::vector<ExtraOption> extra_;
   std::string extra_str_;  // the accepted option string, for the device epilogue
   std::vector<ExtraOption> decode_extra_;

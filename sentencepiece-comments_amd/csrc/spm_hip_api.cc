@@ -68,6 +68,8 @@ hipError_t Upload(spm_amd::DevBuf *buf, const std::vector<T> &v) {
 // ModelInterface::InitializePieces (model_interface.cc:101-144).
 int InitializePieces(spm_hip_model *m) {
   m->unk_id = -1;
+  m->byte_fallback = m->proto.trainer_spec.byte_fallback;
+  std::fill(m->byte_ids, m->byte_ids + 256, -1);
   for (size_t i = 0; i < m->proto.pieces.size(); ++i) {
     const auto &sp = m->proto.pieces[i];
     if (sp.piece.empty()) return Fail(SPM_INTERNAL, "piece must not be empty.");
@@ -81,8 +83,21 @@ int InitializePieces(spm_hip_model *m) {
       if (m->unk_id >= 0) return Fail(SPM_INTERNAL, "unk is already defined.");
       m->unk_id = static_cast<int32_t>(i);
     }
+    // BYTE pieces (byte fallback) are reserved like CONTROL pieces; the byte
+    // of a piece is its name's ("<0x41>"), not its position.
+    if (sp.type == spm_amd::kBytePiece) {
+      if (!m->byte_fallback)
+        return Fail(SPM_INTERNAL, "byte piece " + sp.piece + " is found although `byte_fallback` is false.");
+      const int byte = spm_amd::PieceToByte(sp.piece);
+      if (byte < 0) return Fail(SPM_INTERNAL, "byte piece " + sp.piece + " is invalid.");
+      m->byte_ids[byte] = static_cast<int32_t>(i);
+    }
   }
   if (m->unk_id == -1) return Fail(SPM_INTERNAL, "unk is not defined.");
+  if (m->byte_fallback)
+    for (int b = 0; b < 256; ++b)
+      if (m->byte_ids[b] < 0)
+        return Fail(SPM_INTERNAL, "there are not 256 byte pieces although `byte_fallback` is true.");
   std::sort(m->user_defined.begin(), m->user_defined.end());
   return SPM_OK;
 }
@@ -978,6 +993,7 @@ int BuildDecodeTable(spm_hip_model *m) {
   t.off.assign(v, 0);
   t.bytes.clear();
   t.max_surface = 0;
+  t.has_bytes = false;
   for (size_t i = 0; i < v; ++i) {
     const std::string &piece = m->proto.pieces[i].piece;
     int32_t id = static_cast<int32_t>(i);
@@ -987,6 +1003,14 @@ int BuildDecodeTable(spm_hip_model *m) {
     std::string surface;
     uint32_t strip = 0;
     if (type == spm_amd::kControl) {
+    } else if (type == spm_amd::kBytePiece) {
+      // No table surface: it follows from the byte run around the token
+      // (decode.h, ByteRunSurface).  At most 4 bytes.
+      t.meta[i] = spm_amd::kDecodeByteFlag | static_cast<uint32_t>(spm_amd::PieceToByte(piece));
+      t.off[i] = static_cast<uint32_t>(t.bytes.size());
+      t.max_surface = std::max<uint32_t>(t.max_surface, 4);
+      t.has_bytes = true;
+      continue;
     } else if (type == spm_amd::kUnknown) {
       surface = unk_surface;
     } else {
@@ -1024,9 +1048,12 @@ int EnsureTypes(spm_hip_model *m) {
   for (size_t i = 0; i < types.size(); ++i) {
     const int32_t t = m->proto.pieces[i].type;
     types[i] = (t == spm_amd::kUnknown ? spm_amd::kPieceUnknown : 0) |
-               (t == spm_amd::kControl ? spm_amd::kPieceControl : 0);
+               (t == spm_amd::kControl ? spm_amd::kPieceControl : 0) |
+               (t == spm_amd::kBytePiece ? spm_amd::kPieceByte : 0);
   }
   SPM_HIP_TRY(Upload(&m->d_types, types));
+  if (m->byte_fallback)
+    SPM_HIP_TRY(Upload(&m->d_byte_ids, std::vector<int32_t>(m->byte_ids, m->byte_ids + 256)));
   m->types_ready = true;
   return SPM_OK;
 }
@@ -1138,7 +1165,7 @@ void EncodeWorkspace::Release() {
   if (svc_prof) (void)spm_amd::DevFree(svc_prof);
   svc_prof = nullptr;
   for (DevBuf *b : {&w_ctl, &w_slot_ids, &w_slot_len, &w_tprefix, &w_slot2_ids, &w_slot2_len, &w_ntok, &w_cnt, &w_bp, &w_flagged, &w_ovf, &w_scan,
-                    &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_dfirst, &w_dsum, &w_dctl, &h_dids, &h_dtok, &h_dout, &h_doff, &h_dbegin, &w_tids, &w_tlen, &w_ttok,
+                    &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_dfirst, &w_dsum, &w_dctl, &w_bfsum, &w_bfctl, &h_dids, &h_dtok, &h_dout, &h_doff, &h_dbegin, &w_tids, &w_tlen, &w_ttok,
                     &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask,
                     &w_nb_ctl, &w_nb_npaths, &w_nb_stage, &w_nb_ntok, &w_nb_score, &w_nb_ids, &w_nb_len, &w_nb_hids,
                     &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore, &w_wc_count, &w_wc_first, &w_wc_sent, &w_wc_next, &w_vstat, &w_vcount})
@@ -1363,7 +1390,7 @@ void spm_hip_model_free(spm_hip_model *m) {
   for (spm_amd::DevBuf *b : {&m->d_units, &m->d_uvs, &m->d_piece_tab, &m->d_values, &m->d_scores,
                              &m->bpe.pair_keys, &m->bpe.pair_vals, &m->bpe.pair_ent, &m->bpe.rank_piece, &m->bpe.entry_piece,
                              &m->bpe.entry_out, &m->bpe.piece_kind, &m->bpe.piece_out,
-                             &m->d_wc_tab, &m->d_wc_keys, &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_types_kind, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes})
+                             &m->d_wc_tab, &m->d_wc_keys, &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_byte_ids, &m->d_types_kind, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes})
     b->Release();
   for (auto &kv : m->by_stream) kv.second->Release();
   for (auto &w : m->host_pool) w->Release();
@@ -1798,6 +1825,10 @@ static int FinalizeImpl(spm_hip_model *m, const char *extra_options, const int32
                         const uint64_t *d_tok_off, uint64_t n, int32_t *d_out_ids, uint64_t out_capacity,
                         uint64_t *d_out_off, uint64_t *total, uint32_t *chain, hipStream_t st) {
   if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  if (m->byte_fallback)
+    return Fail(SPM_INVALID_ARGUMENT,
+                "the model uses byte fallback: unknown tokens expand to their bytes, which needs the normalized "
+                "text; call spm_hip_finalize_ids_bytes");
   spm_amd::EpilogueExtras x{};
   {
     const int rc0 = FoldExtras(m, extra_options, &x);
@@ -1860,6 +1891,108 @@ int spm_hip_finalize_ids_async(spm_hip_model *m, const char *extra_options, cons
                       static_cast<hipStream_t>(stream));
 }
 
+// The epilogue of a byte-fallback model (byte_epilogue_kernels.hip).  out_spt
+// selects SentencePieceText pieces (then n2o is norm_to_orig).  chain: the
+// caller's status word, or null for a blocking call.
+static int ByteEpilogueImpl(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd::EpilogueExtras &x,
+                            const int32_t *d_ids, const uint32_t *d_len, const uint64_t *d_tok_off, uint64_t n,
+                            const uint8_t *d_norm, const uint64_t *d_norm_off, int32_t *d_out,
+                            spm_hip_piece *d_out_spt, const uint32_t *d_n2o, uint64_t out_capacity,
+                            uint64_t *d_out_off, uint64_t *total, uint32_t *chain, hipStream_t st) {
+  SPM_HIP_TRY(ws->w_bfsum.Reserve(2 * spm_amd::kDecodeBlocks * sizeof(uint64_t)));
+  SPM_HIP_TRY(ws->w_bfctl.Reserve(2 * sizeof(uint64_t)));
+  uint64_t *ctl = ws->w_bfctl.as<uint64_t>();
+  SPM_HIP_TRY(hipMemsetAsync(ctl, 0, 2 * sizeof(uint64_t), st));
+  spm_amd::ByteEpilogueLaunch a{};
+  a.ids = d_ids;
+  a.len = d_len;
+  a.tok_off = d_tok_off;
+  a.n = n;
+  a.norm = d_norm;
+  a.norm_off = d_norm_off;
+  a.types = m->d_types.as<uint8_t>();
+  a.num_types = static_cast<int32_t>(m->proto.pieces.size());
+  a.byte_ids = m->d_byte_ids.as<int32_t>();
+  a.x = x;
+  a.block_sum = ws->w_bfsum.as<uint64_t>();
+  a.ctl = ctl;
+  a.chain = chain ? chain : reinterpret_cast<uint32_t *>(ctl + 1);  // blocking: a status word of its own
+  a.check_capacity = chain != nullptr;
+  a.capacity = out_capacity;
+  a.out_off = d_out_off;
+  a.out = d_out;
+  a.out_spt = d_out_spt;
+  a.n2o = d_n2o;
+  SPM_HIP_TRY(spm_amd::LaunchByteEpilogueCount(a, st));
+  if (chain) {  // asynchronous: the fill pass checked the capacity
+    if (!d_out && !d_out_spt && out_capacity) return Fail(SPM_INVALID_ARGUMENT, "null output");
+    SPM_HIP_TRY(spm_amd::LaunchByteEpilogueWrite(a, st));
+    return SPM_OK;
+  }
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 12, ctl, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  uint64_t tot = 0;
+  std::memcpy(&tot, ws->pinned + 12, sizeof(uint64_t));
+  if (total) *total = tot;
+  if (tot > out_capacity) return Fail(SPM_RESOURCE_EXHAUSTED, "finalized ids exceed out_capacity");
+  if (tot > 0 && !d_out && !d_out_spt) return Fail(SPM_INVALID_ARGUMENT, "null output");
+  SPM_HIP_TRY(spm_amd::LaunchByteEpilogueWrite(a, st));
+  return SPM_OK;
+}
+
+static int FinalizeBytesImpl(spm_hip_model *m, const char *extra_options, const int32_t *d_ids,
+                             const uint32_t *d_len, const uint64_t *d_tok_off, uint64_t n, const uint8_t *d_norm,
+                             const uint64_t *d_norm_off, int32_t *d_out_ids, uint64_t out_capacity,
+                             uint64_t *d_out_off, uint64_t *total, uint32_t *chain, hipStream_t st) {
+  if (!m->byte_fallback)  // the same result, without reading the text
+    return FinalizeImpl(m, extra_options, d_ids, d_tok_off, n, d_out_ids, out_capacity, d_out_off, total, chain, st);
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  spm_amd::EpilogueExtras x{};
+  int rc = FoldExtras(m, extra_options, &x);
+  if (rc != SPM_OK) return rc;
+  rc = EnsureTypes(m);
+  if (rc != SPM_OK) return rc;
+  if (n == 0) {
+    SPM_HIP_TRY(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), st));
+    if (total) *total = 0;
+    return SPM_OK;
+  }
+  if (!d_ids || !d_len || !d_norm || !d_norm_off) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForStream(m, st));
+  return ByteEpilogueImpl(m, ws.get(), x, d_ids, d_len, d_tok_off, n, d_norm, d_norm_off, d_out_ids, nullptr, nullptr,
+                          out_capacity, d_out_off, total, chain, st);
+}
+
+int spm_hip_finalize_ids_bytes(spm_hip_model *m, const char *extra_options, const int32_t *d_ids,
+                               const uint32_t *d_piece_len, const uint64_t *d_tok_off, uint64_t n,
+                               const uint8_t *d_norm_bytes, const uint64_t *d_norm_off, int32_t *d_out_ids,
+                               uint64_t out_capacity, uint64_t *d_out_off, uint64_t *total, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_finalize_ids_bytes");
+  if (!m || !d_tok_off || !d_out_off) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  return FinalizeBytesImpl(m, extra_options, d_ids, d_piece_len, d_tok_off, n, d_norm_bytes, d_norm_off, d_out_ids,
+                           out_capacity, d_out_off, total, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int spm_hip_finalize_ids_bytes_async(spm_hip_model *m, const char *extra_options, const int32_t *d_ids,
+                                     const uint32_t *d_piece_len, const uint64_t *d_tok_off, uint64_t n,
+                                     const uint8_t *d_norm_bytes, const uint64_t *d_norm_off, int32_t *d_out_ids,
+                                     uint64_t out_capacity, uint64_t *d_out_off, uint32_t *d_status, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_finalize_ids_bytes_async");
+  if (!m || !d_tok_off || !d_out_off || !d_status) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  return FinalizeBytesImpl(m, extra_options, d_ids, d_piece_len, d_tok_off, n, d_norm_bytes, d_norm_off, d_out_ids,
+                           out_capacity, d_out_off, nullptr, d_status, static_cast<hipStream_t>(stream));
+}
+
+int spm_hip_model_byte_fallback(const spm_hip_model *m, int *enabled, int32_t byte_ids[256]) {
+  if (!m || !enabled) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  *enabled = m->byte_fallback ? 1 : 0;
+  if (byte_ids)
+    for (int b = 0; b < 256; ++b) byte_ids[b] = m->byte_fallback ? m->byte_ids[b] : -1;
+  return SPM_OK;
+}
+
 // Host buffers: a pooled workspace with a private stream, so concurrent host
 // calls on one handle run side by side.
 // SentencePieceProcessor::Encode(input, SentencePieceText*) (sentencepiece_
@@ -1899,6 +2032,14 @@ int spm_hip_encode_spt(spm_hip_model *m, const char *extra_options, const uint8_
   rc = EncodeBlocking(m, ws.get(), d_norm, d_norm_off, n, ws->w_tids.as<int32_t>(), ws->w_tlen.as<uint32_t>(),
                   ws->w_ttok.as<uint64_t>(), st);
   if (rc != SPM_OK) return rc;
+  if (m->byte_fallback) {
+    rc = ByteEpilogueImpl(m, ws.get(), x, ws->w_tids.as<int32_t>(), ws->w_tlen.as<uint32_t>(),
+                          ws->w_ttok.as<uint64_t>(), n, d_norm, d_norm_off, nullptr, d_pieces, d_n2o, piece_capacity,
+                          d_piece_off, total_pieces, nullptr, st);
+    if (rc == SPM_RESOURCE_EXHAUSTED) return Fail(SPM_RESOURCE_EXHAUSTED, "pieces exceed piece_capacity");
+    if (rc == SPM_INVALID_ARGUMENT) return Fail(SPM_INVALID_ARGUMENT, "null pieces output");
+    return rc;
+  }
   const int32_t num_types = static_cast<int32_t>(m->proto.pieces.size());
   SPM_HIP_TRY(ws->w_ecount.Reserve(n * sizeof(uint64_t)));
   SPM_HIP_TRY(spm_amd::LaunchEpilogueCount(ws->w_tids.as<int32_t>(), ws->w_ttok.as<uint64_t>(), n,
@@ -2657,8 +2798,10 @@ int spm_hip_encode_raw_small_host(spm_hip_model *m, const uint8_t *raw, const ui
   spm_amd::TraceRange trace_range_("spm_hip_encode_raw_small_host");
   if (!m || !raw_off || !out_off || (n && !raw && raw_off[n])) return Fail(SPM_INVALID_ARGUMENT, "null argument");
   if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  // The fused launch merges unknown runs; under byte fallback they expand
+  // instead (spm_hip_finalize_ids_bytes), so the caller takes the batch path.
   if (n == 0 || n > spm_amd::kCoopSmallMax || raw_off[0] != 0 || raw_off[n] > kSmallMaxBytes / 8 ||
-      m->model_type != spm_amd::kUnigram || m->kernel == spm_amd::UnigramKernel::kGeneralOnly ||
+      m->byte_fallback || m->model_type != spm_amd::kUnigram || m->kernel == spm_amd::UnigramKernel::kGeneralOnly ||
       NeedsHostSized(m) || !m->d_uvs.ptr || m->max_piece_bytes > 56)
     return SPM_UNIMPLEMENTED;
   for (uint64_t i = 0; i < n; ++i)
@@ -2885,6 +3028,7 @@ int DecodeImpl(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd::Ep
   a.off = m->d_dec_off.as<uint32_t>();
   a.bytes = m->d_dec_bytes.as<uint8_t>();
   a.num_pieces = static_cast<int32_t>(m->decode.meta.size());
+  a.has_bytes = m->decode.has_bytes;
   a.x = x;
   a.first = ws->w_dfirst.as<uint32_t>();
   a.block_sum = ws->w_dsum.as<uint64_t>();

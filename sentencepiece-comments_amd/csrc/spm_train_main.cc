@@ -59,7 +59,7 @@ int main(int argc, char **argv) {
       {"control_symbols", ""}, {"user_defined_symbols", ""},
       {"normalization_rule_name", "nmt_nfkc"}, {"normalization_rule_tsv", ""},
       {"add_dummy_prefix", "true"}, {"remove_extra_whitespaces", "true"},
-      {"hard_vocab_limit", "true"}, {"use_all_vocab", "false"}, {"unk_id", "0"},
+      {"hard_vocab_limit", "true"}, {"use_all_vocab", "false"}, {"byte_fallback", "false"}, {"unk_id", "0"},
       {"bos_id", "1"}, {"eos_id", "2"}, {"pad_id", "-1"}, {"unk_piece", "<unk>"},
       {"bos_piece", "<s>"}, {"eos_piece", "</s>"}, {"pad_piece", "<pad>"},
       {"unk_surface", " \xE2\x81\x87 "},
@@ -113,6 +113,14 @@ int main(int argc, char **argv) {
       Status s = SetTrainerField(k, f[k], &ts);
       if (!s.ok()) Die(s.message);
     }
+  // Written into the model only when it is on, so that every other model
+  // keeps the bytes it had before the flag existed.
+  {
+    TrainerSpec probe;
+    Status s = SetTrainerField("byte_fallback", f["byte_fallback"], &probe);
+    if (!s.ok()) Die(s.message);
+    if (probe.byte_fallback) SetTrainerField("byte_fallback", "true", &ts);
+  }
   ns.name = f["normalization_rule_name"];
   ns.has.insert(1);
   for (const char *k : {"normalization_rule_tsv", "add_dummy_prefix", "remove_extra_whitespaces"}) {

@@ -449,6 +449,15 @@ Status UnigramTrainer::InitMetaPieces() {
     if (!insert_meta(w, kControl)) return Err(SPM_INTERNAL, w + " is already defined.");
   for (auto &w : spec_.user_defined_symbols)
     if (!insert_meta(w, kUserDefined)) return Err(SPM_INTERNAL, w + " is already defined.");
+  // Byte fallback: the 256 BYTE pieces follow, score 0 like every meta piece.
+  // Nothing else changes: they count as meta pieces wherever the vocabulary
+  // size is derived.
+  if (spec_.byte_fallback)
+    for (int b = 0; b < 256; ++b) {
+      char w[8];
+      std::snprintf(w, sizeof(w), "<0x%02X>", b);
+      if (!insert_meta(w, kBytePiece)) return Err(SPM_INTERNAL, std::string(w) + " is already defined.");
+    }
   return Status::Ok();
 }
 
@@ -2925,6 +2934,7 @@ Status SetTrainerField(const std::string &k, const std::string &v, TrainerSpec *
   if (k == "user_defined_symbols") return rep(31, &s->user_defined_symbols);
   if (k == "hard_vocab_limit") return bl(33, &s->hard_vocab_limit);
   if (k == "use_all_vocab") return bl(34, &s->use_all_vocab);
+  if (k == "byte_fallback") return bl(35, &s->byte_fallback);
   if (k == "unk_id") return i32(40, &s->unk_id);
   if (k == "bos_id") return i32(41, &s->bos_id);
   if (k == "eos_id") return i32(42, &s->eos_id);
@@ -3053,6 +3063,7 @@ std::string SerializeModelProto(const std::vector<PieceRec> &pieces, const Train
   for (auto &x : ts.user_defined_symbols) PutBytes(31, x, &t);
   if (has(33)) PutBool(33, ts.hard_vocab_limit, &t);
   if (has(34)) PutBool(34, ts.use_all_vocab, &t);
+  if (has(35)) PutBool(35, ts.byte_fallback, &t);
   if (has(40)) PutInt32(40, ts.unk_id, &t);
   if (has(41)) PutInt32(41, ts.bos_id, &t);
   if (has(42)) PutInt32(42, ts.eos_id, &t);

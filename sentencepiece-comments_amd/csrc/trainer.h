@@ -53,6 +53,7 @@ struct TrainerSpec {
   std::vector<std::string> user_defined_symbols;
   bool hard_vocab_limit = true;
   bool use_all_vocab = false;
+  bool byte_fallback = false;  // field 35: 256 BYTE pieces "<0x00>" ... "<0xFF>" among the meta pieces
   int32_t unk_id = 0, bos_id = 1, eos_id = 2, pad_id = -1;
   std::string unk_surface = " \xE2\x81\x87 ";
   std::string unk_piece = "<unk>", bos_piece = "<s>", eos_piece = "</s>", pad_piece = "<pad>";

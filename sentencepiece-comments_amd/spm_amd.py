@@ -53,6 +53,7 @@ EXPORTED = [
     "spm_hip_nbest_last_stats",
     "spm_hip_model_set_piece_types", "spm_hip_model_get_piece_types", "spm_hip_model_set_vocabulary",
     "spm_hip_model_reset_vocabulary", "spm_hip_count_ids", "spm_hip_count_ids_host",
+    "spm_hip_model_byte_fallback", "spm_hip_finalize_ids_bytes", "spm_hip_finalize_ids_bytes_async",
 ]
 
 ABI_VERSION = 3  # SPM_HIP_ABI_VERSION of include/spm_hip.h (struct layouts below)
@@ -150,6 +151,10 @@ def lib():
         L.spm_hip_encode_batch_async.argtypes = [P, P, P, U64, U64, P, P, P, P, P]
         L.spm_hip_normalize_batch_device_async.argtypes = [P, P, P, U64, P, U64, P, P, P, P]
         L.spm_hip_finalize_ids_async.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, P]
+        L.spm_hip_finalize_ids_bytes.argtypes = [P, ctypes.c_char_p, P, P, P, U64, P, P, P, U64, P,
+                                                 ctypes.POINTER(U64), P]
+        L.spm_hip_finalize_ids_bytes_async.argtypes = [P, ctypes.c_char_p, P, P, P, U64, P, P, P, U64, P, P, P]
+        L.spm_hip_model_byte_fallback.argtypes = [P, ctypes.POINTER(I), P]
         L.spm_hip_model_drain_kernel_times.argtypes = [P, P, P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         L.spm_hip_model_set_debug_corrupt_bp.argtypes = [P, ctypes.c_int64]
         L.spm_hip_model_set_coop_min_nb.argtypes = [P, ctypes.c_uint32]
@@ -704,6 +709,45 @@ class DeviceModel:
                                             ctypes.c_void_p(stream) if stream else None))
         return tot.value
 
+    def byte_fallback(self):
+        """spm_hip_model_byte_fallback: None for a model without byte fallback,
+        else the int32[256] table byte -> id of its BYTE piece."""
+        on = ctypes.c_int()
+        ids = np.zeros(256, dtype=np.int32)
+        _check(self._L.spm_hip_model_byte_fallback(self.h, ctypes.byref(on), _p(ids)))
+        return ids if on.value else None
+
+    def is_byte(self, piece_id):
+        """SentencePieceProcessor::IsByte: the id is a BYTE piece of a byte-fallback model."""
+        t = self.byte_fallback()
+        return t is not None and int(piece_id) in set(t.tolist())
+
+    def finalize_ids_bytes_device(self, extra_options, d_ids, d_len, d_tok, n, d_norm, d_norm_off, d_out,
+                                  out_capacity, d_out_off, stream=None):
+        """spm_hip_finalize_ids_bytes on device pointers (under byte fallback
+        an unknown token becomes one BYTE id per byte); returns the output id
+        count.  RESOURCE_EXHAUSTED raises SpmError with the count in `total`."""
+        V = ctypes.c_void_p
+        tot = ctypes.c_uint64()
+        rc = self._L.spm_hip_finalize_ids_bytes(self.h, extra_options.encode(), V(d_ids), V(d_len), V(d_tok), n,
+                                                V(d_norm), V(d_norm_off), V(d_out) if d_out else None,
+                                                out_capacity, V(d_out_off), ctypes.byref(tot),
+                                                V(stream) if stream else None)
+        if rc != SPM_OK:
+            err = SpmError(rc, self._L.spm_hip_last_error().decode(errors="replace"))
+            err.total = tot.value
+            raise err
+        return tot.value
+
+    def finalize_ids_bytes_device_async(self, extra_options, d_ids, d_len, d_tok, n, d_norm, d_norm_off, d_out,
+                                        out_capacity, d_out_off, d_status, stream=None):
+        """spm_hip_finalize_ids_bytes_async: pure stream call, failures land in d_status."""
+        V = ctypes.c_void_p
+        _check(self._L.spm_hip_finalize_ids_bytes_async(self.h, extra_options.encode(), V(d_ids), V(d_len),
+                                                        V(d_tok), n, V(d_norm), V(d_norm_off),
+                                                        V(d_out) if d_out else None, out_capacity, V(d_out_off),
+                                                        V(d_status), V(stream) if stream else None))
+
     def decode_bound(self):
         """spm_hip_model_decode_bound: the longest surface of any id, in bytes."""
         b = ctypes.c_uint32()
@@ -796,15 +840,22 @@ class DeviceModel:
                                                       d_norm.data_ptr(), cap, d_noff.data_ptr(),
                                                       ctypes.byref(tot), s))
         d_ids = torch.empty(max(tot.value, 1), dtype=torch.int32, device=dev)
+        bf = self.byte_fallback() is not None
+        d_len = torch.empty(max(tot.value, 1), dtype=torch.int32, device=dev) if bf else None
         d_tok = torch.empty(n + 1, dtype=torch.int64, device=dev)
         self.encode_device(d_norm.data_ptr(), d_noff.data_ptr(), n, d_ids.data_ptr(), d_tok.data_ptr(),
-                           stream=s)
+                           d_len=d_len.data_ptr() if bf else None, stream=s)
         n_extra = sum(1 for o in extra_options.split(":") if o in ("bos", "eos"))
         ocap = tot.value + n * n_extra
         d_out = torch.empty(max(ocap, 1), dtype=torch.int32, device=dev)
         d_ooff = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        k = self.finalize_ids_device(extra_options, d_ids.data_ptr(), d_tok.data_ptr(), n, d_out.data_ptr(),
-                                     ocap, d_ooff.data_ptr(), stream=s)
+        if not bf:
+            k = self.finalize_ids_device(extra_options, d_ids.data_ptr(), d_tok.data_ptr(), n, d_out.data_ptr(),
+                                         ocap, d_ooff.data_ptr(), stream=s)
+        else:
+            k = self.finalize_ids_bytes_device(extra_options, d_ids.data_ptr(), d_len.data_ptr(), d_tok.data_ptr(),
+                                               n, d_norm.data_ptr(), d_noff.data_ptr(), d_out.data_ptr(), ocap,
+                                               d_ooff.data_ptr(), stream=s)
         torch.cuda.synchronize(dev)
         out = d_out[:k].cpu().numpy()
         oo = d_ooff.cpu().numpy()
