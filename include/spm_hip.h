@@ -230,6 +230,83 @@ int spm_hip_sample_encode_batch_host(spm_hip_model *model, const uint8_t *norm_b
  * `seed`, the stream above (*u in [0, 1), a multiple of 2^-53). */
 int spm_hip_sample_uniform(uint64_t seed, uint64_t index, uint64_t draw, double *u);
 
+/* Batched SentencePieceProcessor::CalculateEntropy of the `sentencepiece`
+ * package (0.2.x): the entropy of every sentence's segmentation distribution
+ * at inverse temperature theta, DEVICE pointers, unigram models.
+ *
+ * Lattice and forward pass A[p]: those of spm_hip_sample_encode_batch above.
+ * One float H[p] per char position: H[0] = 0 and, over the nodes (b, p) in
+ * ascending b (end_nodes_ order), with s the node's score,
+ *   lp   = fl(fl(fl(theta * s) + A[b]) - A[p])
+ *   H[p] = fl(H[p] + fl((float) exp((double) lp) * fl(H[b] + lp))).
+ * d_entropy[i] = -H[len]; d_log_z[i] (nullable) = A[len], the log partition
+ * at theta.  An empty sentence gives -0.0f and log partition 0.  The package
+ * takes exp in float; on the package's own fixtures the two agree in all bits
+ * on more than 99 % of the lines and within a few units in the last place
+ * on the rest.
+ *
+ * BLOCKING.  Status: theta not finite -> SPM_INVALID_ARGUMENT; a model that
+ * is not unigram -> SPM_UNIMPLEMENTED; a host-only handle ->
+ * SPM_FAILED_PRECONDITION.  spm_hip_model_last_stats reports general_path =
+ * the sentences the exact (literal lattice) kernel took: those with a trie
+ * leaf inside a UTF-8 char, or all of them under
+ * spm_hip_model_set_force_general.  Both kernels run the same float
+ * operations in the same order and agree bit for bit. */
+int spm_hip_entropy_batch(spm_hip_model *model, const uint8_t *d_norm_bytes, const uint64_t *d_offsets,
+                          uint64_t n, float theta, float *d_entropy, float *d_log_z, void *stream);
+/* Same contract with HOST buffers (offsets start at 0). */
+int spm_hip_entropy_batch_host(spm_hip_model *model, const uint8_t *norm_bytes, const uint64_t *offsets,
+                               uint64_t n, float theta, float *entropy, float *log_z);
+
+/* Batched SampleEncodeAndScore of the package, sampling with replacement
+ * (wor = false, include_best = false): num_samples segmentations per sentence
+ * drawn as spm_hip_sample_encode_batch draws one, each with its
+ * log-probability.  The forward pass runs once per sentence, the backward
+ * walk num_samples times.
+ *
+ * Rows: row i * num_samples + j is sample j of sentence i.
+ *   d_tok_offsets : uint64[n * num_samples + 1], row r owns tokens
+ *                   [tok_offsets[r], tok_offsets[r + 1])
+ *   d_ids / d_piece_len (nullable) : token_capacity entries
+ *   d_scores      : float[n * num_samples]
+ * token_capacity = num_samples * offsets[n] always suffices.  When the rows
+ * hold more tokens than token_capacity the call returns
+ * SPM_RESOURCE_EXHAUSTED with d_tok_offsets and d_scores written (so
+ * tok_offsets[n * num_samples] is the need) and d_ids / d_piece_len untouched.
+ *
+ * Score of a row, all float: T = 0, T = fl(T + fl(theta * s)) over the row's
+ * nodes from the first to the last, score = fl(T - A[len]).  A row of an
+ * empty sentence has no tokens and score 0.
+ *
+ * Random stream: sample j of the sentence with global index g = index_base +
+ * i depends on (seed, g, j) alone.  With mix and the constants of
+ * spm_hip_sample_encode_batch,
+ *   seed_0 = seed,  seed_j = mix(seed + 0xD1B54A32D192ED03 * j) for j > 0,
+ *   key = mix(seed_j + 0x9E3779B97F4A7C15 * (g + 1)),
+ * and the draws of the walk follow from the key as above.  So sample 0 is
+ * exactly spm_hip_sample_encode_batch's result for (seed, index_base), and
+ * sample j is its result for (seed_j, index_base); spm_hip_sample_seed gives
+ * seed_j to the host, and spm_hip_sample_uniform(seed_j, g, k, &u) the draws.
+ *
+ * BLOCKING.  Status: theta not finite or num_samples == 0 ->
+ * SPM_INVALID_ARGUMENT; n * num_samples >= 2^31 - 1 -> SPM_OUT_OF_RANGE; a
+ * model that is not unigram -> SPM_UNIMPLEMENTED; a host-only handle ->
+ * SPM_FAILED_PRECONDITION.  Tiers and spm_hip_model_last_stats as for
+ * spm_hip_sample_encode_batch. */
+int spm_hip_sample_encode_and_score_batch(spm_hip_model *model, const uint8_t *d_norm_bytes,
+                                          const uint64_t *d_offsets, uint64_t n, uint32_t num_samples,
+                                          float theta, uint64_t seed, uint64_t index_base, int32_t *d_ids,
+                                          uint64_t token_capacity, uint32_t *d_piece_len,
+                                          uint64_t *d_tok_offsets, float *d_scores, void *stream);
+/* Same contract with HOST buffers (offsets start at 0). */
+int spm_hip_sample_encode_and_score_batch_host(spm_hip_model *model, const uint8_t *norm_bytes,
+                                               const uint64_t *offsets, uint64_t n, uint32_t num_samples,
+                                               float theta, uint64_t seed, uint64_t index_base, int32_t *ids,
+                                               uint64_t token_capacity, uint32_t *piece_len,
+                                               uint64_t *tok_offsets, float *scores);
+/* Host only: seed_j of the stream above. */
+int spm_hip_sample_seed(uint64_t seed, uint64_t sample, uint64_t *seed_out);
+
 /* Batched unigram::Model::NBestEncode (unigram_model.cc:729-753 over
  * Lattice::NBest :339-478): the nbest_size best segmentations of every
  * sentence, DEVICE pointers.  Output is model level, like

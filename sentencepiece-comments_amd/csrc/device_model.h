@@ -49,6 +49,9 @@ struct EncodeWorkspace {
   // chosen lnode lengths, and its list of sentences left to the general kernel.
   DevBuf w_cpv, w_cnd, w_crest, w_cpart;
   DevBuf w_salpha, w_smask;  // sampler fast tier: alpha and node-distance mask per byte position
+  // Lattice scores: H (entropy) or the chosen nodes (sample and score) per
+  // byte position; the host entries' entropy / score and log-partition rows.
+  DevBuf w_lpath, w_lscore, w_llogz;
   // NBestEncode: control words, per-sentence path counts and staging starts,
   // per-path token counts and scores, token staging (device tiers / host
   // tier), second-tier overflow list, offsets and gathered scores.

@@ -214,6 +214,89 @@ struct SampleExactArgs {
 };
 hipError_t LaunchUnigramSampleExact(const SampleExactArgs &a, hipStream_t st);
 
+// Unigram lattice scores (unigram_lattice_score.hip): the entropy of every
+// sentence's segmentation distribution, and num_samples drawn segmentations
+// per sentence with their log-probabilities, over the sampler's forward pass
+// A[p].  Two tiers each, bit-identical, with the sampler's flag / overflow /
+// error contract (SampleFastArgs, SampleExactArgs).
+//
+// Entropy, fast tier: A and H per byte position, capacity + n + 1 floats each
+// (position q of sentence i at off[i] + i + q; the launcher fills A with the
+// "no node yet" pattern and zeroes H).  entropy[i] = -H[len]; log_z[i] =
+// A[len] when log_z is set.  A sentence with a trie leaf inside a UTF-8 char
+// is flagged.
+struct EntropyFastArgs {
+  const uint8_t *bytes;
+  const uint64_t *off;
+  uint64_t n;
+  uint64_t capacity;
+  const uint32_t *units;  // the plain double array
+  const int32_t *values;
+  const float *scores;
+  uint32_t num_units;
+  UnigramParams p;
+  float theta;
+  float *A;
+  float *H;
+  float *entropy;         // n
+  float *log_z;           // n, nullable
+  uint32_t *flagged;      // n entries
+  uint32_t *status;       // kStWords
+};
+hipError_t LaunchUnigramEntropyFast(const EntropyFastArgs &a, hipStream_t st);
+
+struct EntropyExactArgs {
+  const uint8_t *bytes;
+  const uint64_t *off;
+  const uint32_t *units;
+  const int32_t *values;
+  const float *scores;
+  uint32_t num_units;
+  UnigramParams p;
+  float theta;
+  float *entropy;
+  float *log_z;           // nullable
+  const uint32_t *list;
+  const uint32_t *count;
+  uint64_t list_n;
+  uint8_t *scratch;
+  uint64_t slab_bytes;
+  uint32_t max_nb;
+  uint32_t *ovf_list;
+  uint32_t *ovf_count;
+  uint32_t *error;
+  uint32_t lanes;
+};
+hipError_t LaunchUnigramEntropyExact(const EntropyExactArgs &a, hipStream_t st);
+
+// Sample and score: the sampler's arguments, num_samples walks per sentence.
+// Row r = i * num_samples + j is sample j of sentence i: its tokens are
+// right-aligned in entries [num_samples * off[i] + j * nb, .. + nb) of
+// slot_ids / slot_len (nb = the sentence's bytes), its count in ntok[r] and
+// its score in score[r].  X (fast tier): capacity + n + 1 words, the chosen
+// node per begin position of the walk at hand.
+struct ScoreFastArgs {
+  SampleFastArgs s;
+  uint32_t num_samples;
+  uint64_t *X;
+  float *score;
+};
+hipError_t LaunchUnigramScoreFast(const ScoreFastArgs &a, hipStream_t st);
+struct ScoreExactArgs {
+  SampleExactArgs s;
+  uint32_t num_samples;
+  float *score;
+};
+hipError_t LaunchUnigramScoreExact(const ScoreExactArgs &a, hipStream_t st);
+
+// Rows of ntok (n * num_samples of them) scanned into tok_off (rows + 1), and
+// the rows' tokens gathered from the slots into ids / piece_len (nullable).
+hipError_t LaunchScoreScan(const uint32_t *ntok, uint64_t rows, uint64_t *tok_off, void *tmp, size_t *tmp_bytes,
+                           hipStream_t st);
+hipError_t LaunchScoreGather(const uint64_t *off, uint64_t n, uint32_t num_samples, const int32_t *slot_ids,
+                             const uint32_t *slot_len, const uint64_t *tok_off, int32_t *ids, uint32_t *piece_len,
+                             hipStream_t st);
+
 // Unigram NBestEncode (unigram_nbest.hip): the n best segmentations of every
 // sentence (Lattice::NBest, unigram_model.cc:339-478), one sentence per lane
 // over a list (list == nullptr: all list_n sentences).  Per-lane slabs of

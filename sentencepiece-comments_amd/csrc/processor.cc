@@ -377,11 +377,167 @@ namespace {
 enum { kIn, kInOff, kNorm, kNormOff, kIds, kLen, kTok, kOut, kOutOff, kSmallBlockSlot, kCounts };
 }  // namespace
 
+// CalculateEntropy of the `sentencepiece` package, batched: the device
+// normalizer, then spm_hip_entropy_batch.
+Status SentencePieceProcessor::CalculateEntropy(const std::vector<std::string> &inputs, float alpha,
+                                                std::vector<float> *entropy) const {
+  if (!status_.ok()) return status_;
+  if (!entropy) return Err(SPM_INTERNAL, "output container is null");
+  if (host_only_) return Err(SPM_FAILED_PRECONDITION, "host-only processor");
+  if (proto_.trainer_spec.model_type != kUnigram)
+    return Err(SPM_INTERNAL, "CalculateEntropy is not available for the current model.");
+  const uint64_t n = inputs.size();
+  entropy->assign(n, 0.f);
+  if (n == 0) return Status::Ok();
+  uint8_t *d_norm = nullptr;
+  uint64_t *d_norm_off = nullptr;
+  uint64_t total = 0;
+  Status st = DeviceNormalize(inputs, &d_norm, &d_norm_off, &total);
+  if (!st.ok()) return st;
+  float *d_h = static_cast<float *>(dev_.Get(kOut, n * 4));
+  if (!d_h) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+  st = FromC(spm_hip_entropy_batch(model_, d_norm, d_norm_off, n, alpha, d_h, nullptr, nullptr));
+  if (!st.ok()) return st;
+  const hipError_t he = hipMemcpy(entropy->data(), d_h, n * 4, hipMemcpyDeviceToHost);
+  return he == hipSuccess ? Status::Ok() : Err(SPM_INTERNAL, hipGetErrorString(he));
+}
+
+Status SentencePieceProcessor::CalculateEntropy(const std::string &input, float alpha, float *entropy) const {
+  if (!entropy) return Err(SPM_INTERNAL, "output container is null");
+  std::vector<float> out;
+  const Status st = CalculateEntropy(std::vector<std::string>{input}, alpha, &out);
+  if (st.ok()) *entropy = out[0];
+  return st;
+}
+
+// SampleEncodeAndScore of the package with wor = false, batched: the device
+// normalizer, spm_hip_sample_encode_and_score_batch, then
+// PopulateSentencePieceText on every sample.
+Status SentencePieceProcessor::SampleEncodeAndScoreBatch(
+    const std::vector<std::string> &inputs, int num_samples, float alpha, bool wor, bool include_best,
+    std::vector<std::vector<std::pair<std::vector<int>, float>>> *ids,
+    std::vector<std::vector<std::pair<std::vector<std::string>, float>>> *pieces) const {
+  if (!status_.ok()) return status_;
+  if (host_only_) return Err(SPM_FAILED_PRECONDITION, "host-only processor");
+  if (proto_.trainer_spec.model_type != kUnigram)
+    return Err(SPM_INTERNAL, "SampleEncodeAndScore is not available for the current model.");
+  if (wor || include_best)
+    return Err(SPM_UNIMPLEMENTED,
+               "SampleEncodeAndScore without replacement (wor, include_best) is not implemented on the device; "
+               "use wor=false, include_best=false");
+  if (num_samples <= 0) return Err(SPM_INTERNAL, "SampleEncodeAndScore returns empty result.");
+  const uint64_t n = inputs.size(), ns = static_cast<uint64_t>(num_samples), rows = n * ns;
+  if (ids) ids->assign(n, {});
+  if (pieces) pieces->assign(n, {});
+  if (n == 0) return Status::Ok();
+  if (!sample_seeded_) {
+    std::random_device rd;
+    sample_seed_ = (static_cast<uint64_t>(rd()) << 32) | rd();
+    sample_seeded_ = true;
+  }
+  uint8_t *d_norm = nullptr;
+  uint64_t *d_norm_off = nullptr;
+  uint64_t total = 0;
+  Status st = DeviceNormalize(inputs, &d_norm, &d_norm_off, &total);
+  if (!st.ok()) return st;
+  const uint64_t cap = std::max<uint64_t>(total * ns, 1);
+  int32_t *d_ids = static_cast<int32_t *>(dev_.Get(kIds, cap * 4));
+  uint32_t *d_len = static_cast<uint32_t *>(dev_.Get(kLen, cap * 4));
+  uint64_t *d_tok = static_cast<uint64_t *>(dev_.Get(kTok, (rows + 1) * 8));
+  float *d_sc = static_cast<float *>(dev_.Get(kOut, rows * 4));
+  if (!d_ids || !d_len || !d_tok || !d_sc) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+  st = FromC(spm_hip_sample_encode_and_score_batch(model_, d_norm, d_norm_off, n, static_cast<uint32_t>(ns), alpha,
+                                                   sample_seed_, sample_count_, d_ids, cap, d_len, d_tok, d_sc,
+                                                   nullptr));
+  if (!st.ok()) return st;
+  sample_count_ += n;
+  auto fail_hip = [](hipError_t e) { return Err(SPM_INTERNAL, hipGetErrorString(e)); };
+  hipError_t he;
+  std::vector<uint64_t> norm_off(n + 1), tok_off(rows + 1);
+  std::vector<float> sc(rows);
+  if ((he = hipMemcpy(norm_off.data(), d_norm_off, (n + 1) * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (he = hipMemcpy(tok_off.data(), d_tok, (rows + 1) * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (he = hipMemcpy(sc.data(), d_sc, rows * 4, hipMemcpyDeviceToHost)) != hipSuccess)
+    return fail_hip(he);
+  const uint64_t ntok = tok_off[rows];
+  std::vector<int32_t> tok_ids(std::max<uint64_t>(ntok, 1));
+  std::vector<uint32_t> tok_len(std::max<uint64_t>(ntok, 1));
+  const bool need_norm = pieces || proto_.trainer_spec.byte_fallback;
+  std::vector<uint8_t> norm(need_norm ? std::max<uint64_t>(total, 1) : 0);
+  if ((he = hipMemcpy(tok_ids.data(), d_ids, ntok * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (he = hipMemcpy(tok_len.data(), d_len, ntok * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (need_norm && (he = hipMemcpy(norm.data(), d_norm, total, hipMemcpyDeviceToHost)) != hipSuccess))
+    return fail_hip(he);
+  std::vector<std::pair<std::string, int>> spt;
+  for (uint64_t i = 0; i < n; ++i) {
+    // The package's model returns no sample for an empty normalized text.
+    if (norm_off[i + 1] == norm_off[i]) return Err(SPM_INTERNAL, "SampleEncodeAndScore returns empty result.");
+    const char *normalized = need_norm ? reinterpret_cast<const char *>(norm.data()) + norm_off[i] : nullptr;
+    for (uint64_t j = 0; j < ns; ++j) {
+      const uint64_t r = i * ns + j;
+      Status ps = PopulateText(normalized, norm_off[i + 1] - norm_off[i], tok_ids.data() + tok_off[r],
+                               tok_len.data() + tok_off[r], tok_off[r + 1] - tok_off[r], &spt);
+      if (!ps.ok()) return ps;
+      if (ids) {
+        (*ids)[i].emplace_back(std::vector<int>(), sc[r]);
+        for (auto &p : spt) (*ids)[i].back().first.push_back(p.second);
+      }
+      if (pieces) {
+        (*pieces)[i].emplace_back(std::vector<std::string>(), sc[r]);
+        for (auto &p : spt) (*pieces)[i].back().first.push_back(std::move(p.first));
+      }
+    }
+  }
+  return Status::Ok();
+}
+
+Status SentencePieceProcessor::SampleEncodeAndScore(const std::string &input, int num_samples, float alpha, bool wor,
+                                                    bool include_best,
+                                                    std::vector<std::pair<std::vector<int>, float>> *ids) const {
+  if (!ids) return Err(SPM_INTERNAL, "output container is null");
+  std::vector<std::vector<std::pair<std::vector<int>, float>>> out;
+  Status st = SampleEncodeAndScoreBatch({input}, num_samples, alpha, wor, include_best, &out, nullptr);
+  if (st.ok()) *ids = std::move(out[0]);
+  return st;
+}
+
+Status SentencePieceProcessor::SampleEncodeAndScore(
+    const std::string &input, int num_samples, float alpha, bool wor, bool include_best,
+    std::vector<std::pair<std::vector<std::string>, float>> *pieces) const {
+  if (!pieces) return Err(SPM_INTERNAL, "output container is null");
+  std::vector<std::vector<std::pair<std::vector<std::string>, float>>> out;
+  Status st = SampleEncodeAndScoreBatch({input}, num_samples, alpha, wor, include_best, nullptr, &out);
+  if (st.ok()) *pieces = std::move(out[0]);
+  return st;
+}
+
 // Raw lines -> device; Normalizer::Normalize and ModelInterface::Encode (or
 // the sampler) run on the device over the whole batch.  *b: the device
 // buffers of the normalized bytes and the model-level tokens.
 Status SentencePieceProcessor::DeviceEncode(const std::vector<std::string> &inputs, const SampleSpec *sample,
                                             DeviceBatch *b) const {
+  const uint64_t n = inputs.size();
+  uint8_t *d_norm = nullptr;
+  uint64_t *d_norm_off = nullptr;
+  uint64_t total = 0;
+  Status st = DeviceNormalize(inputs, &d_norm, &d_norm_off, &total);
+  if (!st.ok()) return st;
+  uint64_t *d_tok = static_cast<uint64_t *>(dev_.Get(kTok, (n + 1) * 8));
+  int32_t *d_ids = static_cast<int32_t *>(dev_.Get(kIds, std::max<uint64_t>(total, 1) * 4));
+  uint32_t *d_len = static_cast<uint32_t *>(dev_.Get(kLen, std::max<uint64_t>(total, 1) * 4));
+  if (!d_tok || !d_ids || !d_len) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+  st = FromC(sample ? spm_hip_sample_encode_batch(model_, d_norm, d_norm_off, n, sample->theta, sample->seed,
+                                                  sample->index_base, d_ids, d_len, d_tok, nullptr)
+                    : spm_hip_encode_batch(model_, d_norm, d_norm_off, n, d_ids, d_len, d_tok, nullptr));
+  if (!st.ok()) return st;
+  *b = DeviceBatch{d_norm, d_norm_off, d_ids, d_len, d_tok, total};
+  return Status::Ok();
+}
+
+// Raw lines -> device and Normalizer::Normalize over the whole batch: the
+// normalized bytes, their offsets (dev_'s buffers) and their number.
+Status SentencePieceProcessor::DeviceNormalize(const std::vector<std::string> &inputs, uint8_t **d_norm_out,
+                                               uint64_t **d_norm_off_out, uint64_t *total_out) const {
   const uint64_t n = inputs.size();
   std::vector<uint64_t> in_off(n + 1, 0);
   for (uint64_t i = 0; i < n; ++i) in_off[i + 1] = in_off[i] + inputs[i].size();
@@ -392,8 +548,7 @@ Status SentencePieceProcessor::DeviceEncode(const std::vector<std::string> &inpu
   uint8_t *d_in = static_cast<uint8_t *>(dev_.Get(kIn, in_off[n]));
   uint64_t *d_in_off = static_cast<uint64_t *>(dev_.Get(kInOff, (n + 1) * 8));
   uint64_t *d_norm_off = static_cast<uint64_t *>(dev_.Get(kNormOff, (n + 1) * 8));
-  uint64_t *d_tok = static_cast<uint64_t *>(dev_.Get(kTok, (n + 1) * 8));
-  if (!d_in || !d_in_off || !d_norm_off || !d_tok) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+  if (!d_in || !d_in_off || !d_norm_off) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
   hipError_t he;
   if ((he = hipMemcpy(d_in, in_bytes.data(), in_off[n], hipMemcpyHostToDevice)) != hipSuccess ||
       (he = hipMemcpy(d_in_off, in_off.data(), (n + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess)
@@ -411,14 +566,9 @@ Status SentencePieceProcessor::DeviceEncode(const std::vector<std::string> &inpu
   }
   Status st = FromC(rc);
   if (!st.ok()) return st;
-  int32_t *d_ids = static_cast<int32_t *>(dev_.Get(kIds, std::max<uint64_t>(total, 1) * 4));
-  uint32_t *d_len = static_cast<uint32_t *>(dev_.Get(kLen, std::max<uint64_t>(total, 1) * 4));
-  if (!d_ids || !d_len) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
-  st = FromC(sample ? spm_hip_sample_encode_batch(model_, d_norm, d_norm_off, n, sample->theta, sample->seed,
-                                                  sample->index_base, d_ids, d_len, d_tok, nullptr)
-                    : spm_hip_encode_batch(model_, d_norm, d_norm_off, n, d_ids, d_len, d_tok, nullptr));
-  if (!st.ok()) return st;
-  *b = DeviceBatch{d_norm, d_norm_off, d_ids, d_len, d_tok, total};
+  *d_norm_out = d_norm;
+  *d_norm_off_out = d_norm_off;
+  *total_out = total;
   return Status::Ok();
 }
 

@@ -79,6 +79,32 @@ class SentencePieceProcessor {
   // sentence counter.
   void SetRandomSeed(uint64_t seed);
 
+  // CalculateEntropy of the `sentencepiece` package: the entropy of a line's
+  // segmentation distribution at inverse temperature alpha, from the device
+  // (spm_hip_entropy_batch).  A model that is not unigram gives INTERNAL
+  // "CalculateEntropy is not available for the current model.".
+  Status CalculateEntropy(const std::string &input, float alpha, float *entropy) const;
+  Status CalculateEntropy(const std::vector<std::string> &inputs, float alpha, std::vector<float> *entropy) const;
+
+  // SampleEncodeAndScore of the package: num_samples segmentations of a line
+  // drawn from the unigram lattice, each with its log-probability
+  // (spm_hip_sample_encode_and_score_batch).  Unknown-run merge, extra
+  // options and the byte epilogue apply as in SampleEncode, and the lines'
+  // global indices advance as there, so a fixed seed replays.  wor or
+  // include_best (sampling without replacement) gives SPM_UNIMPLEMENTED; a
+  // model that is not unigram gives INTERNAL "SampleEncodeAndScore is not
+  // available for the current model."; a line whose normalized text is empty
+  // gives INTERNAL "SampleEncodeAndScore returns empty result.", as in the
+  // package.
+  Status SampleEncodeAndScore(const std::string &input, int num_samples, float alpha, bool wor, bool include_best,
+                              std::vector<std::pair<std::vector<int>, float>> *ids) const;
+  Status SampleEncodeAndScore(const std::string &input, int num_samples, float alpha, bool wor, bool include_best,
+                              std::vector<std::pair<std::vector<std::string>, float>> *pieces) const;
+  Status SampleEncodeAndScoreBatch(const std::vector<std::string> &inputs, int num_samples, float alpha, bool wor,
+                                   bool include_best,
+                                   std::vector<std::vector<std::pair<std::vector<int>, float>>> *ids,
+                                   std::vector<std::vector<std::pair<std::vector<std::string>, float>>> *pieces) const;
+
   // NBestEncode (sentencepiece_processor.cc:588-609), batched: the nbest_size
   // (clamped to [1, 1024]) best segmentations of every line, best first, from
   // the device A* search (spm_hip_nbest_encode_batch); a line with fewer
@@ -210,6 +236,8 @@ class SentencePieceProcessor {
     uint64_t total = 0;  // normalized bytes
   };
   Status DeviceEncode(const std::vector<std::string> &inputs, const SampleSpec *sample, DeviceBatch *b) const;
+  Status DeviceNormalize(const std::vector<std::string> &inputs, uint8_t **d_norm, uint64_t **d_norm_off,
+                         uint64_t *total) const;
   Status DeviceFinalize(const DeviceBatch &b, uint64_t n, int32_t **d_out, uint64_t **d_out_off, uint64_t *fin) const;
   // EncodeBatch; with `sample` the device sampler stands in for the encode.
   Status RunBatch(const std::vector<std::string> &inputs, std::vector<std::vector<int>> *ids,

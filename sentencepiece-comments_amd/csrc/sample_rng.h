@@ -26,6 +26,14 @@ SPM_RNG_FN uint64_t SampleMix(uint64_t z) {
 // Key of the sentence with global index g.
 SPM_RNG_FN uint64_t SampleKey(uint64_t seed, uint64_t g) { return SampleMix(seed + kSampleGolden * (g + 1)); }
 
+// Seed of sample j of a sample-and-score call: sample 0 keeps the caller's
+// seed (so it is SampleEncode's draw), sample j > 0 takes a seed of its own;
+// its key is SampleKey(SampleSeedAt(seed, j), g).
+constexpr uint64_t kSampleStride = 0xD1B54A32D192ED03ull;
+SPM_RNG_FN uint64_t SampleSeedAt(uint64_t seed, uint64_t j) {
+  return j == 0 ? seed : SampleMix(seed + kSampleStride * j);
+}
+
 // Draw k of a sentence: a multiple of 2^-53 in [0, 1).
 SPM_RNG_FN double SampleDraw(uint64_t key, uint64_t k) {
   return static_cast<double>(SampleMix(key + kSampleGolden * (k + 1)) >> 11) * 0x1.0p-53;

@@ -1166,7 +1166,7 @@ void EncodeWorkspace::Release() {
   svc_prof = nullptr;
   for (DevBuf *b : {&w_ctl, &w_slot_ids, &w_slot_len, &w_tprefix, &w_slot2_ids, &w_slot2_len, &w_ntok, &w_cnt, &w_bp, &w_flagged, &w_ovf, &w_scan,
                     &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_dfirst, &w_dsum, &w_dctl, &w_bfsum, &w_bfctl, &h_dids, &h_dtok, &h_dout, &h_doff, &h_dbegin, &w_tids, &w_tlen, &w_ttok,
-                    &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask,
+                    &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask, &w_lpath, &w_lscore, &w_llogz,
                     &w_nb_ctl, &w_nb_npaths, &w_nb_stage, &w_nb_ntok, &w_nb_score, &w_nb_ids, &w_nb_len, &w_nb_hids,
                     &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore, &w_wc_count, &w_wc_first, &w_wc_sent, &w_wc_next, &w_vstat, &w_vcount})
     b->Release();
@@ -2897,6 +2897,328 @@ int spm_hip_sample_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, con
                       st);
   if (rc != SPM_OK) return rc;
   return FetchHostBatch(m, ws.get(), n, ids, len, tok, st);
+}
+
+// ---------------------------------------------------------------------------
+// Lattice scores (unigram_lattice_score.hip): CalculateEntropy and
+// SampleEncodeAndScore.
+extern "C++" {  // (LatticeTiers is a template)
+namespace {
+
+int LatticeScoreArgsCheck(const spm_hip_model *m, float theta, const char *what) {
+  if (!std::isfinite(theta)) return Fail(SPM_INVALID_ARGUMENT, "theta must be finite");
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  if (m->model_type != spm_amd::kUnigram)
+    return Fail(SPM_UNIMPLEMENTED, std::string(what) + " is implemented for unigram models only");
+  return SPM_OK;
+}
+
+int HostOffsetsCheck(const uint64_t *off, uint64_t n) {
+  if (off[0] != 0) return Fail(SPM_INVALID_ARGUMENT, "offsets must start at 0");
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
+  return SPM_OK;
+}
+
+// The two tiers of a lattice-score call, SampleBlocking's plan: fast(status)
+// over every sentence, exact(GeneralLaunch) over the sentences it flagged
+// (device-count passes); force_general, or a flagged sentence too long for
+// the device pool, runs the exact tier over every sentence with host-sized
+// scratch.  Waits for the kernels and publishes the tier counts.
+template <typename Fast, typename Exact>
+int LatticeTiers(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint64_t *d_off, uint64_t n, uint64_t cap,
+                 int32_t *s2, uint32_t *s2l, const char *too_long, hipStream_t st, Fast fast, Exact exact) {
+  bool host_sized = m->force_general;
+  uint32_t flagged = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    uint32_t *status = nullptr;
+    int rc = PrepareControl(ws, n, st, &status);
+    if (rc != SPM_OK) return rc;
+    const bool timing = TimedSlot(m, ws) >= 0;
+    if (host_sized) {
+      uint32_t max_nb = 0;
+      rc = LongestSentence(d_off, n, st, &max_nb);
+      if (rc != SPM_OK) return rc;
+      spm_amd::GeneralPool gp;
+      rc = ReserveHostSized(m, ws, n, std::max<uint32_t>(max_nb, 1), too_long, &gp);
+      if (rc != SPM_OK) return rc;
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
+      SPM_HIP_TRY(exact(spm_amd::GeneralLaunch{nullptr, nullptr, n, ws->w_scratch.as<uint8_t>(), gp.slab, gp.small_nb,
+                                               gp.lanes, nullptr, nullptr, status + spm_amd::kStError, s2, s2l,
+                                               ws->w_ntok.as<uint32_t>()}));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
+    } else {
+      SPM_HIP_TRY(ws->w_flagged.Reserve(n * 4));
+      spm_amd::GeneralPool gp;
+      rc = ReserveGeneralPool(m, ws, n, cap, &gp);
+      if (rc != SPM_OK) return rc;
+      const int slot = ws->last_slot;
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot], st));
+      SPM_HIP_TRY(fast(status));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot + 1], st));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
+      rc = LaunchFlaggedPair(ws, gp, ws->w_flagged.as<uint32_t>(), status + spm_amd::kStFlagged, status, s2, s2l,
+                             exact);
+      if (rc != SPM_OK) return rc;
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
+    }
+    SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, status, 4 * (spm_amd::kStError + 1), hipMemcpyDeviceToHost, st));
+    SPM_HIP_TRY(hipStreamSynchronize(st));
+    flagged = ws->pinned[spm_amd::kStFlagged];
+    const uint32_t err = ws->pinned[spm_amd::kStError];
+    if (err == 0) break;
+    // Bit 0: a flagged sentence outgrew the device pool; anything else is a
+    // broken walk, which a second run would only repeat.
+    if (host_sized || err != 1u) return Fail(SPM_INTERNAL, "exact lattice path: scratch overflow or broken walk");
+    host_sized = true;
+  }
+  ws->stats.sentences = n;
+  ws->stats.general_path = host_sized ? n : flagged;
+  if (m->timing && ws->last_slot >= 0) {
+    const int s = ws->last_slot;
+    if (!host_sized) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.fast_kernel_ms, ws->tev[2 * s], ws->tev[2 * s + 1]));
+    if (ws->stats.general_path) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
+    ws->tcount = 0;
+  }
+  spm_amd::PublishStats(m, ws->stats);
+  return SPM_OK;
+}
+
+// offsets[n] of a device batch (one small copy and wait).
+int BatchBytes(spm_amd::EncodeWorkspace *ws, const uint64_t *d_off, uint64_t n, hipStream_t st, uint64_t *total) {
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 8, d_off + n, 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(total, ws->pinned + 8, 8);
+  if (*total > 0xFFFFFFFFull * 4) return Fail(SPM_OUT_OF_RANGE, "batch too large");
+  return SPM_OK;
+}
+
+int EntropyBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *d_bytes, const uint64_t *d_off,
+                    uint64_t n, float theta, float *d_entropy, float *d_log_z, hipStream_t st) {
+  uint64_t total = 0;
+  int rc = BatchBytes(ws, d_off, n, st, &total);
+  if (rc != SPM_OK) return rc;
+  ws->stats = spm_hip_encode_stats{};
+  if (n == 0) {
+    spm_amd::PublishStats(m, ws->stats);
+    return SPM_OK;
+  }
+  const uint64_t cap = std::max<uint64_t>(total, 1);
+  const uint32_t num_units = static_cast<uint32_t>(m->trie.units.size());
+  if (!m->force_general) {
+    SPM_HIP_TRY(ws->w_salpha.Reserve((cap + n + 1) * 4));
+    SPM_HIP_TRY(ws->w_lpath.Reserve((cap + n + 1) * 4));
+  }
+  auto fast = [&](uint32_t *status) {
+    const spm_amd::EntropyFastArgs f{d_bytes, d_off, n, total, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                                     m->d_scores.as<float>(), num_units, m->up, theta, ws->w_salpha.as<float>(),
+                                     ws->w_lpath.as<float>(), d_entropy, d_log_z, ws->w_flagged.as<uint32_t>(),
+                                     status};
+    return spm_amd::LaunchUnigramEntropyFast(f, st);
+  };
+  auto exact = [&](const spm_amd::GeneralLaunch &g) {
+    const spm_amd::EntropyExactArgs x{d_bytes, d_off, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                                      m->d_scores.as<float>(), num_units, m->up, theta, d_entropy, d_log_z, g.list,
+                                      g.count, g.list_n, g.scratch, g.slab_bytes, g.max_nb, g.ovf_list, g.ovf_count,
+                                      g.error, g.threads};
+    return spm_amd::LaunchUnigramEntropyExact(x, st);
+  };
+  return LatticeTiers(m, ws, d_off, n, cap, nullptr, nullptr, "sentence too long for the exact entropy path", st,
+                      fast, exact);
+}
+
+// Sample and score on a leased workspace: the rows' token offsets go to
+// d_tok and the scores to d_scores; *tokens = the rows' token total.  The
+// tokens wait in the workspace's slots for ScoreGatherTo.
+int ScoreBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *d_bytes, const uint64_t *d_off,
+                  uint64_t n, uint32_t ns, float theta, uint64_t seed, uint64_t index_base, bool with_len,
+                  uint64_t *d_tok, float *d_scores, uint64_t *tokens, hipStream_t st) {
+  uint64_t total = 0;
+  int rc = BatchBytes(ws, d_off, n, st, &total);
+  if (rc != SPM_OK) return rc;
+  ws->stats = spm_hip_encode_stats{};
+  *tokens = 0;
+  if (n == 0) {
+    SPM_HIP_TRY(hipMemsetAsync(d_tok, 0, sizeof(uint64_t), st));
+    SPM_HIP_TRY(hipStreamSynchronize(st));
+    spm_amd::PublishStats(m, ws->stats);
+    return SPM_OK;
+  }
+  const uint64_t rows = n * ns;
+  const uint64_t cap = std::max<uint64_t>(total, 1);
+  SPM_HIP_TRY(ws->w_slot2_ids.Reserve(cap * ns * 4));
+  if (with_len) SPM_HIP_TRY(ws->w_slot2_len.Reserve(cap * ns * 4));
+  SPM_HIP_TRY(ws->w_ntok.Reserve(rows * 4));
+  int32_t *s2 = ws->w_slot2_ids.as<int32_t>();
+  uint32_t *s2l = with_len ? ws->w_slot2_len.as<uint32_t>() : nullptr;
+  const uint32_t num_units = static_cast<uint32_t>(m->trie.units.size());
+  if (!m->force_general) {
+    SPM_HIP_TRY(ws->w_salpha.Reserve((cap + n + 1) * 4));
+    SPM_HIP_TRY(ws->w_smask.Reserve((cap + n + 1) * 8));
+    SPM_HIP_TRY(ws->w_lpath.Reserve((cap + n + 1) * 8));
+  }
+  auto fast = [&](uint32_t *status) {
+    const spm_amd::ScoreFastArgs f{
+        spm_amd::SampleFastArgs{d_bytes, d_off, n, total, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                                m->d_scores.as<float>(), num_units, m->up, theta, seed, index_base,
+                                ws->w_salpha.as<float>(), ws->w_smask.as<uint64_t>(), s2, s2l,
+                                ws->w_ntok.as<uint32_t>(), ws->w_flagged.as<uint32_t>(), status},
+        ns, ws->w_lpath.as<uint64_t>(), d_scores};
+    return spm_amd::LaunchUnigramScoreFast(f, st);
+  };
+  auto exact = [&](const spm_amd::GeneralLaunch &g) {
+    const spm_amd::ScoreExactArgs x{
+        spm_amd::SampleExactArgs{d_bytes, d_off, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                                 m->d_scores.as<float>(), num_units, m->up, theta, seed, index_base, g.slot_ids,
+                                 g.slot_len, g.ntok, g.list, g.count, g.list_n, g.scratch, g.slab_bytes, g.max_nb,
+                                 g.ovf_list, g.ovf_count, g.error, g.threads},
+        ns, d_scores};
+    return spm_amd::LaunchUnigramScoreExact(x, st);
+  };
+  rc = LatticeTiers(m, ws, d_off, n, cap, s2, s2l, "sentence too long for the exact sampling path", st, fast, exact);
+  if (rc != SPM_OK) return rc;
+  size_t tmp = 0;
+  SPM_HIP_TRY(spm_amd::LaunchScoreScan(ws->w_ntok.as<uint32_t>(), rows, d_tok, nullptr, &tmp, st));
+  SPM_HIP_TRY(ws->w_scan.Reserve(tmp + 16));
+  SPM_HIP_TRY(spm_amd::LaunchScoreScan(ws->w_ntok.as<uint32_t>(), rows, d_tok, ws->w_scan.ptr, &tmp, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 8, d_tok + rows, 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(tokens, ws->pinned + 8, 8);
+  ws->stats.tokens = *tokens;
+  spm_amd::PublishStats(m, ws->stats);
+  return SPM_OK;
+}
+
+int ScoreGatherTo(spm_amd::EncodeWorkspace *ws, const uint64_t *d_off, uint64_t n, uint32_t ns, const uint64_t *d_tok,
+                  int32_t *d_ids, uint32_t *d_len, hipStream_t st) {
+  SPM_HIP_TRY(spm_amd::LaunchScoreGather(d_off, n, ns, ws->w_slot2_ids.as<int32_t>(),
+                                         d_len ? ws->w_slot2_len.as<uint32_t>() : nullptr, d_tok, d_ids, d_len, st));
+  return SPM_OK;
+}
+
+int ScoreArgsCheck(const spm_hip_model *m, uint64_t n, uint32_t ns, float theta) {
+  if (ns == 0) return Fail(SPM_INVALID_ARGUMENT, "num_samples must be positive");
+  const int rc = LatticeScoreArgsCheck(m, theta, "SampleEncodeAndScore");
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull || n * static_cast<uint64_t>(ns) >= 0x7FFFFFFFull)
+    return Fail(SPM_OUT_OF_RANGE, "too many sample rows in one batch");
+  return SPM_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int spm_hip_entropy_batch(spm_hip_model *m, const uint8_t *d_bytes, const uint64_t *d_off, uint64_t n, float theta,
+                          float *d_entropy, float *d_log_z, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_entropy_batch");
+  if (!m || !d_off || (n && !d_entropy)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  const int rc = LatticeScoreArgsCheck(m, theta, "CalculateEntropy");
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForStream(m, st));
+  return EntropyBlocking(m, ws.get(), d_bytes, d_off, n, theta, d_entropy, d_log_z, st);
+}
+
+int spm_hip_entropy_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint64_t *off, uint64_t n, float theta,
+                               float *entropy, float *log_z) {
+  spm_amd::TraceRange trace_range_("spm_hip_entropy_batch_host");
+  if (!m || !off || (n && !entropy)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  int rc = LatticeScoreArgsCheck(m, theta, "CalculateEntropy");
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  if ((rc = HostOffsetsCheck(off, n)) != SPM_OK) return rc;
+  const uint64_t total = off[n];
+  if (total && !bytes) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForHost(m));
+  hipStream_t st = ws.stream();
+  SPM_HIP_TRY(ws->h_in.Reserve(std::max<uint64_t>(total, 1)));
+  SPM_HIP_TRY(ws->h_off.Reserve((n + 1) * 8));
+  SPM_HIP_TRY(ws->w_lscore.Reserve(std::max<uint64_t>(n, 1) * 4));
+  if (log_z) SPM_HIP_TRY(ws->w_llogz.Reserve(std::max<uint64_t>(n, 1) * 4));
+  if (total) SPM_HIP_TRY(hipMemcpyAsync(ws->h_in.ptr, bytes, total, hipMemcpyHostToDevice, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->h_off.ptr, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  rc = EntropyBlocking(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), n, theta,
+                       ws->w_lscore.as<float>(), log_z ? ws->w_llogz.as<float>() : nullptr, st);
+  if (rc != SPM_OK || n == 0) return rc;
+  SPM_HIP_TRY(hipMemcpyAsync(entropy, ws->w_lscore.ptr, n * 4, hipMemcpyDeviceToHost, st));
+  if (log_z) SPM_HIP_TRY(hipMemcpyAsync(log_z, ws->w_llogz.ptr, n * 4, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  return SPM_OK;
+}
+
+int spm_hip_sample_encode_and_score_batch(spm_hip_model *m, const uint8_t *d_bytes, const uint64_t *d_off, uint64_t n,
+                                          uint32_t num_samples, float theta, uint64_t seed, uint64_t index_base,
+                                          int32_t *d_ids, uint64_t token_capacity, uint32_t *d_len, uint64_t *d_tok,
+                                          float *d_scores, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_sample_encode_and_score_batch");
+  if (!m || !d_off || !d_tok || (n && !d_scores)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  int rc = ScoreArgsCheck(m, n, num_samples, theta);
+  if (rc != SPM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForStream(m, st));
+  uint64_t T = 0;
+  rc = ScoreBlocking(m, ws.get(), d_bytes, d_off, n, num_samples, theta, seed, index_base, d_len != nullptr, d_tok,
+                     d_scores, &T, st);
+  if (rc != SPM_OK) return rc;
+  if (T > token_capacity) return Fail(SPM_RESOURCE_EXHAUSTED, "sampled tokens exceed the caller's capacity");
+  if (T && !d_ids) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (T == 0) return SPM_OK;
+  rc = ScoreGatherTo(ws.get(), d_off, n, num_samples, d_tok, d_ids, d_len, st);
+  if (rc != SPM_OK) return rc;
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  return SPM_OK;
+}
+
+int spm_hip_sample_encode_and_score_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                                               uint32_t num_samples, float theta, uint64_t seed, uint64_t index_base,
+                                               int32_t *ids, uint64_t token_capacity, uint32_t *len, uint64_t *tok,
+                                               float *scores) {
+  spm_amd::TraceRange trace_range_("spm_hip_sample_encode_and_score_batch_host");
+  if (!m || !off || !tok || (n && !scores)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  int rc = ScoreArgsCheck(m, n, num_samples, theta);
+  if (rc != SPM_OK) return rc;
+  if ((rc = HostOffsetsCheck(off, n)) != SPM_OK) return rc;
+  const uint64_t total = off[n];
+  if (total && !bytes) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  const uint64_t rows = n * num_samples;
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForHost(m));
+  hipStream_t st = ws.stream();
+  SPM_HIP_TRY(ws->h_in.Reserve(std::max<uint64_t>(total, 1)));
+  SPM_HIP_TRY(ws->h_off.Reserve((n + 1) * 8));
+  SPM_HIP_TRY(ws->h_tok.Reserve((rows + 1) * 8));
+  SPM_HIP_TRY(ws->w_lscore.Reserve(std::max<uint64_t>(rows, 1) * 4));
+  if (total) SPM_HIP_TRY(hipMemcpyAsync(ws->h_in.ptr, bytes, total, hipMemcpyHostToDevice, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->h_off.ptr, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  uint64_t T = 0;
+  rc = ScoreBlocking(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), n, num_samples, theta, seed,
+                     index_base, len != nullptr, ws->h_tok.as<uint64_t>(), ws->w_lscore.as<float>(), &T, st);
+  if (rc != SPM_OK) return rc;
+  SPM_HIP_TRY(hipMemcpyAsync(tok, ws->h_tok.ptr, (rows + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (rows) SPM_HIP_TRY(hipMemcpyAsync(scores, ws->w_lscore.ptr, rows * 4, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  if (T > token_capacity) return Fail(SPM_RESOURCE_EXHAUSTED, "sampled tokens exceed the caller's capacity");
+  if (T && !ids) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (T == 0) return SPM_OK;
+  SPM_HIP_TRY(ws->h_ids.Reserve(T * 4));
+  if (len) SPM_HIP_TRY(ws->h_len.Reserve(T * 4));
+  rc = ScoreGatherTo(ws.get(), ws->h_off.as<uint64_t>(), n, num_samples, ws->h_tok.as<uint64_t>(),
+                     ws->h_ids.as<int32_t>(), len ? ws->h_len.as<uint32_t>() : nullptr, st);
+  if (rc != SPM_OK) return rc;
+  SPM_HIP_TRY(hipMemcpyAsync(ids, ws->h_ids.ptr, T * 4, hipMemcpyDeviceToHost, st));
+  if (len) SPM_HIP_TRY(hipMemcpyAsync(len, ws->h_len.ptr, T * 4, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  return SPM_OK;
+}
+
+int spm_hip_sample_seed(uint64_t seed, uint64_t sample, uint64_t *seed_out) {
+  if (!seed_out) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  *seed_out = spm_amd::SampleSeedAt(seed, sample);
+  return SPM_OK;
 }
 
 int spm_hip_nbest_encode_batch(spm_hip_model *m, const uint8_t *d_bytes, const uint64_t *d_off, uint64_t n,

@@ -49,6 +49,8 @@ EXPORTED = [
     "spm_hip_estep_kernel_times", "spm_hip_device_bytes", "spm_hip_device_peak_reset",
     "spm_hip_encode_raw_small_host", "spm_hip_model_piece_lookup",
     "spm_hip_sample_encode_batch", "spm_hip_sample_encode_batch_host", "spm_hip_sample_uniform",
+    "spm_hip_entropy_batch", "spm_hip_entropy_batch_host", "spm_hip_sample_encode_and_score_batch",
+    "spm_hip_sample_encode_and_score_batch_host", "spm_hip_sample_seed",
     "spm_hip_nbest_encode_batch", "spm_hip_nbest_encode_batch_host", "spm_hip_model_set_nbest_max_hyps",
     "spm_hip_nbest_last_stats",
     "spm_hip_model_set_piece_types", "spm_hip_model_get_piece_types", "spm_hip_model_set_vocabulary",
@@ -214,6 +216,13 @@ def lib():
         L.spm_hip_sample_encode_batch.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P, P]
         L.spm_hip_sample_encode_batch_host.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P]
         L.spm_hip_sample_uniform.argtypes = [U64, U64, U64, ctypes.POINTER(ctypes.c_double)]
+        L.spm_hip_entropy_batch.argtypes = [P, P, P, U64, ctypes.c_float, P, P, P]
+        L.spm_hip_entropy_batch_host.argtypes = [P, P, P, U64, ctypes.c_float, P, P]
+        L.spm_hip_sample_encode_and_score_batch.argtypes = [P, P, P, U64, ctypes.c_uint32, ctypes.c_float, U64, U64,
+                                                            P, U64, P, P, P, P]
+        L.spm_hip_sample_encode_and_score_batch_host.argtypes = [P, P, P, U64, ctypes.c_uint32, ctypes.c_float, U64,
+                                                                 U64, P, U64, P, P, P]
+        L.spm_hip_sample_seed.argtypes = [U64, U64, ctypes.POINTER(U64)]
         I32 = ctypes.c_int32
         L.spm_hip_nbest_encode_batch.argtypes = [P, P, P, U64, I32, P, P, U64, P, P, U64, P, ctypes.POINTER(U64),
                                                  ctypes.POINTER(U64), P]
@@ -267,6 +276,15 @@ def sample_uniform(seed, index, draw):
     m = (1 << 64) - 1
     _check(lib().spm_hip_sample_uniform(seed & m, index & m, draw & m, ctypes.byref(u)))
     return u.value
+
+
+def sample_seed(seed, sample):
+    """The seed of sample `sample` of a sample-and-score call under `seed`
+    (spm_hip_sample_seed); sample 0 keeps the seed."""
+    out = ctypes.c_uint64()
+    m = (1 << 64) - 1
+    _check(lib().spm_hip_sample_seed(seed & m, sample & m, ctypes.byref(out)))
+    return out.value
 
 
 def to_csr(items):
@@ -569,6 +587,57 @@ class DeviceModel:
                                                    ctypes.c_void_p(d_len) if d_len else None,
                                                    ctypes.c_void_p(d_tok),
                                                    ctypes.c_void_p(stream) if stream else None))
+
+    def entropy_csr_host(self, buf, off, theta, with_log_z=False):
+        """CalculateEntropy of host CSR sentences at inverse temperature theta:
+        float32[n][, the log partition float32[n]]."""
+        n = len(off) - 1
+        h = np.zeros(max(n, 1), dtype=np.float32)
+        z = np.zeros(max(n, 1), dtype=np.float32) if with_log_z else None
+        _check(self._L.spm_hip_entropy_batch_host(self.h, _p(buf), _p(off), n, theta, _p(h),
+                                                  _p(z) if with_log_z else None))
+        return (h[:n], z[:n]) if with_log_z else h[:n]
+
+    def entropy_device(self, d_bytes, d_off, n, theta, d_entropy, d_log_z=None, stream=None):
+        """spm_hip_entropy_batch on device pointers (ints); blocking."""
+        _check(self._L.spm_hip_entropy_batch(self.h, ctypes.c_void_p(d_bytes), ctypes.c_void_p(d_off), n, theta,
+                                             ctypes.c_void_p(d_entropy),
+                                             ctypes.c_void_p(d_log_z) if d_log_z else None,
+                                             ctypes.c_void_p(stream) if stream else None))
+
+    def sample_encode_and_score_csr_host(self, buf, off, num_samples, theta, seed, index_base=0, with_lens=False,
+                                         token_capacity=None):
+        """SampleEncodeAndScore (wor=False) of host CSR sentences: num_samples
+        drawn segmentations per sentence with their log-probabilities.  Row
+        i * num_samples + j is sample j of sentence i.  Returns (ids int32,
+        tok_off uint64[rows + 1], scores float32[rows][, piece_len uint32]).
+        token_capacity defaults to what always suffices; a smaller one raises
+        SpmError (code 8, with .tok_offsets and .scores set)."""
+        n = len(off) - 1
+        rows = n * int(num_samples)
+        cap = int(num_samples) * int(off[-1]) if token_capacity is None else int(token_capacity)
+        ids = np.zeros(max(cap, 1), dtype=np.int32)
+        lens = np.zeros(max(cap, 1), dtype=np.uint32) if with_lens else None
+        to = np.zeros(rows + 1, dtype=np.uint64)
+        sc = np.zeros(max(rows, 1), dtype=np.float32)
+        rc = self._L.spm_hip_sample_encode_and_score_batch_host(self.h, _p(buf), _p(off), n, int(num_samples), theta,
+                                                                seed, index_base, _p(ids), cap,
+                                                                _p(lens) if with_lens else None, _p(to), _p(sc))
+        if rc != SPM_OK:
+            e = SpmError(rc, self._L.spm_hip_last_error().decode(errors="replace"))
+            e.tok_offsets, e.scores = to, sc[:rows]
+            raise e
+        k = int(to[-1])
+        out = (ids[:k], to, sc[:rows])
+        return out + (lens[:k],) if with_lens else out
+
+    def sample_encode_and_score_device(self, d_bytes, d_off, n, num_samples, theta, seed, d_ids, token_capacity,
+                                       d_tok, d_scores, index_base=0, d_len=None, stream=None):
+        """spm_hip_sample_encode_and_score_batch on device pointers (ints); blocking."""
+        _check(self._L.spm_hip_sample_encode_and_score_batch(
+            self.h, ctypes.c_void_p(d_bytes), ctypes.c_void_p(d_off), n, int(num_samples), theta, seed, index_base,
+            ctypes.c_void_p(d_ids), token_capacity, ctypes.c_void_p(d_len) if d_len else None,
+            ctypes.c_void_p(d_tok), ctypes.c_void_p(d_scores), ctypes.c_void_p(stream) if stream else None))
 
     def nbest_encode_csr_host(self, buf, off, nbest_size, with_lens=False, capacities=None):
         """NBestEncode of host CSR sentences: the nbest_size best segmentations
