@@ -161,7 +161,17 @@ int spm_hip_encode_batch_async(spm_hip_model *model, const uint8_t *d_norm_bytes
                                void *stream);
 
 /* Same contract with HOST buffers; stages through pooled device buffers and
- * returns after the results are copied back. */
+ * returns after the results are copied back.  Small calls of a unigram model
+ * (<= 16 sentences: one cooperative launch; <= 256: one tile of the fast
+ * kernel) read the input from and write the results to pinned memory.  A BPE
+ * model's calls of <= 16 sentences take one launch too (bpe_small_kernel, one
+ * wave per sentence) when SPM_HIP_BPE_SMALL_HOST=1 is set: every sentence of
+ * <= 1024 bytes is taken; a longer one, a merge that pushes an UNUSED piece
+ * and, on a model some of whose pieces hold a char that is no piece itself, a
+ * char outside the vocabulary hand the call to the staged path, whose stats
+ * then carry coop_rest = n.  Models with USER_DEFINED pieces and
+ * force_general never try it.  After 8 such calls in a row the launch is
+ * skipped, and tried again on every 64th call. */
 int spm_hip_encode_batch_host(spm_hip_model *model, const uint8_t *norm_bytes,
                               const uint64_t *offsets, uint64_t n, int32_t *ids,
                               uint32_t *piece_len, uint64_t *tok_offsets);
@@ -898,15 +908,26 @@ int spm_hip_model_piece_lookup(const spm_hip_model *model, const uint8_t *bytes,
 
 /* Raw lines -> the final ids of SentencePieceProcessor::Encode(line, &ids)
  * (sentencepiece_processor.cc:319-330: Normalizer::Normalize, normalizer.cc:
- * 88-211; ModelInterface::Encode, unigram_model.cc:705-720; the unknown-run
- * merge of PopulateSentencePieceText, :488-551) with no extra options, for
- * 1..16 lines of a unigram model in ONE device launch: raw image up and ids
- * down through pinned host memory, one completion word polled (the per-line
- * path of spm_encode_main.cc:189-191).  ids_cap entries in ids, n + 1 offsets
- * in out_off.  SPM_UNIMPLEMENTED: the fused path does not take this call (a
- * BPE model, more lines, a line of > 1024 bytes, a sentence whose lattice
- * needs the general kernel): run spm_hip_normalize_batch_device +
- * spm_hip_encode_batch + spm_hip_finalize_ids instead, nothing was written.
+ * 88-211; ModelInterface::Encode, unigram_model.cc:705-720 / bpe_model.cc:
+ * 37-199; the unknown-run merge of PopulateSentencePieceText, :488-551) with
+ * no extra options, for 1..16 lines of a unigram or BPE model in ONE device
+ * launch: raw image up and ids down through pinned host memory, one
+ * completion word polled (the per-line path of spm_encode_main.cc:189-191).
+ * ids_cap entries in ids, n + 1 offsets in out_off.  SPM_UNIMPLEMENTED: the
+ * fused path does not take this call, nothing was written: run
+ * spm_hip_normalize_batch_device + spm_hip_encode_batch + spm_hip_finalize_ids
+ * instead.  Never taken: more lines, a line of > 1024 bytes, a WORD or CHAR
+ * model, a byte-fallback model, force_general, a unigram model without a fast
+ * kernel, a BPE model with USER_DEFINED pieces.  Unigram: not taken when a
+ * sentence's lattice needs the general kernel.  BPE (bpe_raw_kernel, one wave
+ * per line): not taken when a line's normalized form has > 1024 bytes, when a
+ * merge pushes an UNUSED piece (a restricted vocabulary: it needs the general
+ * kernel's resegmentation) and, on a model some of whose pieces hold a char
+ * that is no piece itself, on a char outside the vocabulary; after 8 such
+ * calls in a row the launch is skipped (SPM_UNIMPLEMENTED at once), every
+ * 64th call tries again, a taken call and spm_hip_model_set_piece_types start
+ * the count over.  A BPE call's stats: sentences = n; tokens when taken;
+ * coop_rest = n when the kernel ran and handed the call back.
  * SPM_RESOURCE_EXHAUSTED: more ids than ids_cap (4 * raw bytes + 8 * n + 64
  * always suffices). */
 int spm_hip_encode_raw_small_host(spm_hip_model *model, const uint8_t *raw, const uint64_t *raw_off,

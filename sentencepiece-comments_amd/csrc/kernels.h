@@ -473,6 +473,43 @@ struct CoopCall {
   uint32_t *len;        // small: piece byte lengths (nullable)
   uint32_t *host_pub;   // [0] sequence, [1] 0 = done, 1 = not taken
 };
+// BPE small calls (bpe_line.hip): one block, n <= kCoopSmallMax lines, one
+// wave per line, one launch per call.  bpe_small_kernel takes normalized
+// sentences (the staged image [offsets | bytes], sentence i at bytes + in_at +
+// off[i]) and writes tok, ids and len; bpe_raw_kernel takes raw lines (image
+// [raw offsets | raw bytes], line i's normalized bytes at bytes + 4 raw_off[i]
+// + 8 i as in CoopRawArgs), merges unknown runs and writes tok (out_off) and
+// ids.  A wave's tokens wait in slot_ids / slot_len from the sentence's byte
+// offset on.  A line of more than kBpeLineMaxBytes normalized bytes, a pushed
+// UNUSED piece or (irregular models) a char outside the vocabulary publishes
+// "not taken" (host_pub[1] = 1) and writes no output.
+constexpr uint32_t kBpeLineMaxBytes = 1024;
+struct BpeLineArgs {
+  const uint32_t *units;       // the symbol trie
+  const int32_t *values;       // leaf -> entry index
+  const int32_t *entry_piece;
+  const int32_t *entry_out;
+  const int32_t *piece_out;
+  const uint4 *pair_ent;       // (right id, left id, merged id | unused << 31, score rank)
+  uint64_t pair_mask;
+  uint32_t root_base;
+  int32_t unk_id;
+  int32_t irregular;
+  const uint8_t *bytes;        // small: the staged image; raw: the normalized bytes (written)
+  int32_t *slot_ids;
+  uint32_t *slot_len;          // small only
+  const uint32_t *stage_src;
+  uint32_t *stage_dst;
+};
+struct BpeRawArgs {
+  BpeLineArgs a;
+  NormTables t;
+  const uint8_t *types;        // piece type bits (epilogue.h), num_types entries
+  int32_t num_types;
+};
+hipError_t LaunchBpeSmall(const BpeLineArgs &a, const CoopCall &c, hipStream_t st);
+hipError_t LaunchBpeRaw(const BpeRawArgs &s, const CoopCall &c, hipStream_t st);
+
 // Resident service kernel for small calls (coop_service_kernel): one block
 // polls `box` in pinned coherent host memory; the host writes `call` and
 // then `seq` = (sequence & 0x3FFFFFFF) | kind << 30 (kind 1 = normalized

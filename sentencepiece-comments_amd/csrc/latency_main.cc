@@ -10,9 +10,11 @@
 //   * spm_hip_encode_batch_host over B normalized sentences per call, for a
 //     range of B — the batch size at which the device adapter beats the
 //     reference's per-sentence cost.
-// Prints one JSON object.
+// Prints one JSON object.  With `single` only the first figure is taken (the
+// batch sweeps make calls x 351 encodes of their own, which on a file of long
+// lines takes minutes).
 //
-//   spm_latency MODEL LINES_FILE [calls]
+//   spm_latency MODEL LINES_FILE [calls] [single]
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -37,8 +39,9 @@ double Now() {
 }  // namespace
 
 int main(int argc, char **argv) {
-  if (argc < 3) Die("usage: spm_latency MODEL LINES_FILE [calls]");
+  if (argc < 3) Die("usage: spm_latency MODEL LINES_FILE [calls] [single]");
   const int calls = argc > 3 ? std::atoi(argv[3]) : 2000;
+  const bool single = argc > 4 && std::string(argv[4]) == "single";
   std::ifstream in(argv[2], std::ios::binary);
   if (!in) Die("cannot read lines");
   std::vector<std::string> lines;
@@ -60,6 +63,12 @@ int main(int argc, char **argv) {
     toks += ids.size();
   }
   const double proc_us = (Now() - t0) * 1e6 / calls;
+  if (single) {
+    std::printf("{\"calls\": %d, \"encode_single_us\": %.3f, \"encode_single_tokens\": %llu, \"lines\": %llu}\n",
+                calls, proc_us, static_cast<unsigned long long>(toks),
+                static_cast<unsigned long long>(lines.size()));
+    return 0;
+  }
   // The whole file as one EncodeBatch(ids) call (raw lines -> device
   // normalize, encode and id epilogue -> host ids), best of a few.
   std::vector<std::vector<int>> all;

@@ -11,8 +11,10 @@ namespace spm_amd {
 // kRaw: 1..kCoopSmallMax raw lines (coop_raw_kernel).  kCoop: as many
 // normalized sentences (coop_small_kernel).  kLane: up to 256 normalized
 // sentences, one tile of the lane kernels, whose zeroed control block
-// (ctl_bytes) leads the device mirror.
-enum class SmallKind { kRaw, kCoop, kLane };
+// (ctl_bytes) leads the device mirror.  kBpeRaw / kBpe: the images of kRaw /
+// kCoop for a BPE model (bpe_raw_kernel, bpe_small_kernel), which keep no
+// per-char tables beside the token slots.
+enum class SmallKind { kRaw, kCoop, kLane, kBpeRaw, kBpe };
 
 // Every region starts on a 256-byte boundary.  The kernels read the input in
 // 16-byte steps, so 16 bytes of pad follow it; they index token slots and
@@ -29,6 +31,7 @@ struct SmallLayout {
   uint64_t pub;      // 256 B: publication word, status words, late status copy
   uint64_t ids_cap;  // ids (and lengths) the image has room for
   uint64_t slots;    // raw, coop: rows of the cooperative kernel's device tables (0: lane)
+  uint64_t table_slots;  // of them, rows of its per-char tables (w_cpv, w_cnd); 0: lane and the BPE kinds
   uint64_t slot_len_bytes;  // device bytes beside the id slots: coop piece lengths, raw normalized bytes
   uint64_t dev_bytes;  // to reserve for the device mirror
   uint64_t pin_bytes;  // to reserve for the pinned image
@@ -59,7 +62,8 @@ constexpr uint64_t SmallAlign(uint64_t x) { return (x + 255) & ~255ull; }
 // kLane only with_len.
 constexpr SmallLayout MakeSmallLayout(SmallKind kind, uint64_t n, uint64_t total, bool with_len = false,
                                       uint64_t ctl_bytes = 0) {
-  const bool raw = kind == SmallKind::kRaw, lane = kind == SmallKind::kLane;
+  const bool bpe = kind == SmallKind::kBpeRaw || kind == SmallKind::kBpe;
+  const bool raw = kind == SmallKind::kRaw || kind == SmallKind::kBpeRaw, lane = kind == SmallKind::kLane;
   SmallLayout l{};
   l.off = lane ? SmallAlign(ctl_bytes) : 0;
   l.in = SmallAlign(l.off + (n + 1) * 8);
@@ -68,12 +72,13 @@ constexpr SmallLayout MakeSmallLayout(SmallKind kind, uint64_t n, uint64_t total
   l.ids = SmallAlign(l.tok + (n + 1) * 8);
   // Raw lines: what the normalizer and the encode can make of them at most.
   l.ids_cap = raw ? 4 * total + 8 * n + 64 : (total ? total : 1);
-  const bool has_len = kind == SmallKind::kCoop || (lane && with_len);
+  const bool has_len = kind == SmallKind::kCoop || kind == SmallKind::kBpe || (lane && with_len);
   l.len = has_len ? SmallAlign(l.ids + l.ids_cap * 4) : 0;
   l.out_end = (has_len ? l.len : l.ids) + l.ids_cap * 4;
   l.pub = SmallAlign(l.out_end);
   l.pin_bytes = l.pub + 256;
   l.slots = raw ? l.ids_cap : lane ? 0 : l.in_end + 16;
+  l.table_slots = bpe ? 0 : l.slots;
   l.slot_len_bytes = raw ? l.slots : l.slots * 4;
   // The lane kernels address their outputs through the mirror's offsets too.
   l.dev_bytes = lane ? l.out_end : l.in_end + 16;
@@ -113,6 +118,14 @@ static_assert(kR2.in == 256 && kR2.tok == 512 && kR2.ids == 768 && kR2.ids_cap =
 constexpr SmallLayout kR3 = MakeSmallLayout(SmallKind::kRaw, 16, 16384);
 static_assert(kR3.tok == 16896 && kR3.ids == 17152 && kR3.ids_cap == 65728 && kR3.pub == 280064 &&
               kR3.pin_bytes == 280320, "");
+constexpr SmallLayout kB1 = MakeSmallLayout(SmallKind::kBpe, 1, 95);
+static_assert(kB1.off == 0 && kB1.in == 256 && kB1.tok == 512 && kB1.ids == 768 && kB1.len == 1280 &&
+              kB1.pub == 1792 && kB1.pin_bytes == 2048 && kB1.slots == 367 && kB1.table_slots == 0 &&
+              kB1.slot_len_bytes == 1468 && kB1.dev_bytes == 367 && kC1.table_slots == 367, "");
+constexpr SmallLayout kB2 = MakeSmallLayout(SmallKind::kBpeRaw, 1, 95);
+static_assert(kB2.off == 0 && kB2.in == 256 && kB2.tok == 512 && kB2.ids == 768 && kB2.ids_cap == 452 &&
+              kB2.slots == 452 && kB2.table_slots == 0 && kB2.slot_len_bytes == 452 && kB2.pub == 2816 &&
+              kB2.pin_bytes == 3072 && kB2.dev_bytes == 367 && kR1.table_slots == 452, "");
 }  // namespace small_layout_pins
 
 }  // namespace spm_amd

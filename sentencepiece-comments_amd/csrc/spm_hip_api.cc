@@ -1387,6 +1387,13 @@ int spm_hip_model_load_host_only(const void *model_proto, size_t len, spm_hip_mo
 
 void spm_hip_model_free(spm_hip_model *m) {
   if (!m) return;
+  // SPM_HIP_SMALL_STATS: what became of the handle's BPE small calls (the
+  // processor and the CLIs have no other view of which path served them).
+  if (m->model_type == spm_amd::kBpe && std::getenv("SPM_HIP_SMALL_STATS"))
+    std::fprintf(stderr, "spm_hip: bpe line calls taken=%llu refused=%llu skipped=%llu\n",
+                 static_cast<unsigned long long>(m->bpe_line_taken.load()),
+                 static_cast<unsigned long long>(m->bpe_line_refused.load()),
+                 static_cast<unsigned long long>(m->bpe_line_skipped.load()));
   for (spm_amd::DevBuf *b : {&m->d_units, &m->d_uvs, &m->d_piece_tab, &m->d_values, &m->d_scores,
                              &m->bpe.pair_keys, &m->bpe.pair_vals, &m->bpe.pair_ent, &m->bpe.rank_piece, &m->bpe.entry_piece,
                              &m->bpe.entry_out, &m->bpe.piece_kind, &m->bpe.piece_out,
@@ -2101,7 +2108,8 @@ uint64_t ServiceIdleTicks() {
 // directly, and the host polls that word.
 int ReserveSmall(spm_amd::EncodeWorkspace *ws, const spm_amd::SmallLayout &l) {
   // The lane kind has no slots: FastSetup reserves its work buffers, nothing of these four.
-  const uint64_t rows = l.slots ? (l.slots + 64) * spm_amd::kCoopSlots : 0;
+  // The BPE kinds have slots and no per-char tables.
+  const uint64_t rows = l.table_slots ? (l.table_slots + 64) * spm_amd::kCoopSlots : 0;
   const std::pair<spm_amd::DevBuf *, uint64_t> want[] = {{&ws->w_small, l.dev_bytes},
                                                          {&ws->w_slot2_ids, l.slots * 4},
                                                          {&ws->w_slot2_len, l.slot_len_bytes},
@@ -2344,6 +2352,134 @@ int EncodeHostCoop(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t
     ws->StopService();  // the lane-kernel re-run may share the server's hardware queue
     return SPM_OK;
   }
+  rc = FinishSmall(m, ws, l, n, 0, -1, ids, len, tok);
+  *done = rc == SPM_OK;
+  return rc;
+}
+
+// The model's tables for the BPE line kernels (bpe_line.hip).
+spm_amd::BpeLineArgs BpeLineTables(const spm_hip_model *m) {
+  spm_amd::BpeLineArgs a{};
+  a.units = m->d_units.as<uint32_t>();
+  a.values = m->d_values.as<int32_t>();
+  a.entry_piece = m->bpe.entry_piece.as<int32_t>();
+  a.entry_out = m->bpe.entry_out.as<int32_t>();
+  a.piece_out = m->bpe.piece_out.as<int32_t>();
+  a.pair_ent = m->bpe.pair_ent.as<uint4>();
+  a.pair_mask = m->bpe.pair_mask;
+  a.root_base = m->up.root_base;
+  a.unk_id = m->unk_id;
+  a.irregular = m->bpe.irregular ? 1 : 0;
+  return a;
+}
+
+// Whether a BPE handle's small call tries the line kernel: the back-off of
+// the unigram small calls (coop_small_rejects).  A vocabulary-restricted
+// model, whose merges keep pushing UNUSED pieces, would otherwise pay two
+// round trips on every call: after 8 refusals in a row the kernel is skipped,
+// every 64th call tries again, and a call it takes resets the count.
+bool BpeLineTry(spm_hip_model *m) {
+  const uint32_t rejects = m->coop_small_rejects.load(std::memory_order_relaxed);
+  if (rejects < 8 || rejects % 64 == 0) return true;
+  m->coop_small_rejects.fetch_add(1, std::memory_order_relaxed);
+  m->bpe_line_skipped.fetch_add(1, std::memory_order_relaxed);
+  return false;
+}
+
+// SPM_HIP_BPE_SMALL_HOST=1 (read per call): spm_hip_encode_batch_host sends a
+// BPE model's calls of <= kCoopSmallMax sentences to bpe_small_kernel first.
+bool BpeSmallHostOn() {
+  const char *e = std::getenv("SPM_HIP_BPE_SMALL_HOST");
+  return e && std::atoi(e) != 0;
+}
+
+void BpeLineTried(spm_hip_model *m, bool taken) {
+  if (taken) {
+    m->coop_small_rejects.store(0, std::memory_order_relaxed);
+    m->bpe_line_taken.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    m->coop_small_rejects.fetch_add(1, std::memory_order_relaxed);
+    m->bpe_line_refused.fetch_add(1, std::memory_order_relaxed);
+  }
+}
+
+// One BPE small call: its single launch is on `st` already; the wait for
+// host_pub[0] == c.pub_seq.  *taken = false: the kernel published "not taken".
+int WaitBpeCall(const spm_amd::CoopCall &c, hipStream_t st, const char *what, bool *taken) {
+  bool published = false;
+  const int rc = WaitPublished(c.host_pub, c.pub_seq, st, &published);
+  if (rc != SPM_OK) return rc;
+  if (!published) return Fail(SPM_INTERNAL, std::string(what) + " ended without publishing");
+  *taken = static_cast<volatile uint32_t *>(c.host_pub)[1] == 0;
+  return SPM_OK;
+}
+
+// Raw lines -> final ids of Encode(line, &ids) on a BPE model, in one launch
+// (bpe_raw_kernel) on the workspace's stream: the staging of EncodeRawCoop,
+// no server.  *done = false: a line the kernel does not take (more than
+// kBpeLineMaxBytes normalized bytes, a pushed UNUSED piece, on an irregular
+// model a char outside the vocabulary).  The call's stats say which it was:
+// coop_rest = n when the kernel handed the call back.
+int EncodeRawBpe(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *raw, const uint64_t *raw_off,
+                 uint64_t n, int32_t *ids, uint64_t ids_cap, uint64_t *out_off, hipStream_t st, bool *done) {
+  *done = false;
+  const spm_amd::SmallLayout l = spm_amd::MakeSmallLayout(spm_amd::SmallKind::kBpeRaw, n, raw_off[n]);
+  int rc = ReserveSmall(ws, l);
+  if (rc != SPM_OK) return rc;
+  uint8_t *h = ws->pin_small;
+  uint8_t *d = ws->w_small.as<uint8_t>();
+  l.Stage(h, raw_off, raw, n);
+  spm_amd::BpeLineArgs a = BpeLineTables(m);
+  a.bytes = ws->w_slot2_len.as<uint8_t>();  // normalized bytes
+  a.slot_ids = ws->w_slot2_ids.as<int32_t>();
+  a.stage_src = reinterpret_cast<const uint32_t *>(h);
+  a.stage_dst = reinterpret_cast<uint32_t *>(d);
+  const spm_amd::BpeRawArgs ra{a, DeviceNormTables(m), m->d_types.as<uint8_t>(),
+                               static_cast<int32_t>(m->proto.pieces.size())};
+  const spm_amd::CoopCall c = SmallCoopCall(ws, l, n, false);
+  SPM_HIP_TRY(spm_amd::LaunchBpeRaw(ra, c, st));
+  bool taken = false;
+  if ((rc = WaitBpeCall(c, st, "BPE raw-line encode", &taken)) != SPM_OK) return rc;
+  ws->stats = spm_hip_encode_stats{};
+  ws->stats.sentences = n;
+  if (!taken) {
+    ws->stats.coop_rest = n;
+    spm_amd::PublishStats(m, ws->stats);
+    return SPM_OK;
+  }
+  std::memcpy(out_off, l.Tok(h), (n + 1) * 8);
+  const uint64_t nt = out_off[n];
+  if (nt > ids_cap) return Fail(SPM_RESOURCE_EXHAUSTED, "ids exceed ids_cap");
+  if (nt) std::memcpy(ids, l.Ids(h), nt * 4);
+  ws->stats.tokens = nt;
+  spm_amd::PublishStats(m, ws->stats);
+  *done = true;
+  return SPM_OK;
+}
+
+// Host API, very small batches of a BPE model (n <= kCoopSmallMax): ONE launch
+// of bpe_small_kernel, the image and the outputs as in EncodeHostCoop.
+// *done = false: the caller takes the staged blocking path.
+int EncodeHostBpe(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *bytes, const uint64_t *off,
+                  uint64_t n, int32_t *ids, uint32_t *len, uint64_t *tok, hipStream_t st, bool *done) {
+  *done = false;
+  const spm_amd::SmallLayout l = spm_amd::MakeSmallLayout(spm_amd::SmallKind::kBpe, n, off[n]);
+  int rc = ReserveSmall(ws, l);
+  if (rc != SPM_OK) return rc;
+  uint8_t *h = ws->pin_small;
+  uint8_t *d = ws->w_small.as<uint8_t>();
+  l.Stage(h, off, bytes, n);
+  spm_amd::BpeLineArgs a = BpeLineTables(m);
+  a.bytes = d;
+  a.slot_ids = ws->w_slot2_ids.as<int32_t>();
+  a.slot_len = ws->w_slot2_len.as<uint32_t>();
+  a.stage_src = reinterpret_cast<const uint32_t *>(h);
+  a.stage_dst = reinterpret_cast<uint32_t *>(d);
+  const spm_amd::CoopCall c = SmallCoopCall(ws, l, n, len != nullptr);
+  SPM_HIP_TRY(spm_amd::LaunchBpeSmall(a, c, st));
+  bool taken = false;
+  if ((rc = WaitBpeCall(c, st, "BPE small encode", &taken)) != SPM_OK) return rc;
+  if (!taken) return SPM_OK;
   rc = FinishSmall(m, ws, l, n, 0, -1, ids, len, tok);
   *done = rc == SPM_OK;
   return rc;
@@ -2800,9 +2936,12 @@ int spm_hip_encode_raw_small_host(spm_hip_model *m, const uint8_t *raw, const ui
   if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
   // The fused launch merges unknown runs; under byte fallback they expand
   // instead (spm_hip_finalize_ids_bytes), so the caller takes the batch path.
+  // NeedsHostSized: force_general, a unigram model without a fast kernel, a
+  // BPE model with USER_DEFINED pieces.
+  const bool bpe = m->model_type == spm_amd::kBpe;
   if (n == 0 || n > spm_amd::kCoopSmallMax || raw_off[0] != 0 || raw_off[n] > kSmallMaxBytes / 8 ||
-      m->byte_fallback || m->model_type != spm_amd::kUnigram || m->kernel == spm_amd::UnigramKernel::kGeneralOnly ||
-      NeedsHostSized(m) || !m->d_uvs.ptr || m->max_piece_bytes > 56)
+      m->byte_fallback || (m->model_type != spm_amd::kUnigram && !bpe) || NeedsHostSized(m) ||
+      (!bpe && (!m->d_uvs.ptr || m->max_piece_bytes > 56)))
     return SPM_UNIMPLEMENTED;
   for (uint64_t i = 0; i < n; ++i)
     if (raw_off[i + 1] < raw_off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
@@ -2812,6 +2951,18 @@ int spm_hip_encode_raw_small_host(spm_hip_model *m, const uint8_t *raw, const ui
   spm_amd::WorkspaceLease ws;
   SPM_LEASE(ws, ws.ForHost(m));
   bool done = false;
+  if (bpe) {
+    if (!BpeLineTry(m)) {
+      ws->stats = spm_hip_encode_stats{};
+      ws->stats.sentences = n;
+      spm_amd::PublishStats(m, ws->stats);
+      return SPM_UNIMPLEMENTED;
+    }
+    rc = EncodeRawBpe(m, ws.get(), raw, raw_off, n, ids, ids_cap, out_off, ws.stream(), &done);
+    if (rc != SPM_OK) return rc;
+    BpeLineTried(m, done);
+    return done ? SPM_OK : SPM_UNIMPLEMENTED;
+  }
   rc = EncodeRawCoop(m, ws.get(), raw, raw_off, n, ids, ids_cap, out_off, ws.stream(), &done);
   if (rc != SPM_OK) return rc;
   return done ? SPM_OK : SPM_UNIMPLEMENTED;
@@ -2851,13 +3002,33 @@ int spm_hip_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint
     const int rc = EncodeHostSmall(m, ws.get(), bytes, off, n, ids, len, tok, st, &done);
     if (rc != SPM_OK || done) return rc;
   }
+  // BPE, with SPM_HIP_BPE_SMALL_HOST=1: n <= kCoopSmallMax sentences through
+  // bpe_small_kernel first (one launch); a call it does not take falls to the
+  // staged path below, and the call's stats then carry coop_rest = n.  Off by
+  // default: through this entry the batch tiers' routing (general_path) is
+  // pinned down to batches of one sentence.
+  uint64_t bpe_refused = 0;
+  if (n >= 1 && n <= spm_amd::kCoopSmallMax && total <= kSmallMaxBytes && m->model_type == spm_amd::kBpe &&
+      !NeedsHostSized(m) && BpeSmallHostOn() && BpeLineTry(m)) {
+    bool done = false;
+    const int rc = EncodeHostBpe(m, ws.get(), bytes, off, n, ids, len, tok, st, &done);
+    if (rc != SPM_OK) return rc;
+    BpeLineTried(m, done);
+    if (done) return rc;
+    bpe_refused = n;
+  }
   int rc = StageHostBatch(ws.get(), bytes, off, n, total, len != nullptr, st);
   if (rc != SPM_OK) return rc;
   rc = EncodeBlocking(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), n,
                       ws->h_ids.as<int32_t>(), len ? ws->h_len.as<uint32_t>() : nullptr,
                       ws->h_tok.as<uint64_t>(), st);
   if (rc != SPM_OK) return rc;
-  return FetchHostBatch(m, ws.get(), n, ids, len, tok, st);
+  rc = FetchHostBatch(m, ws.get(), n, ids, len, tok, st);
+  if (rc == SPM_OK && bpe_refused) {
+    ws->stats.coop_rest = bpe_refused;
+    spm_amd::PublishStats(m, ws->stats);
+  }
+  return rc;
 }
 
 int spm_hip_sample_encode_batch(spm_hip_model *m, const uint8_t *d_bytes, const uint64_t *d_off, uint64_t n,
@@ -3529,6 +3700,9 @@ int spm_hip_model_set_piece_types(spm_hip_model *m, const uint8_t *types, uint64
       SPM_HIP_TRY(hipStreamSynchronize(streams[k]));
     }
   }
+  // What the small calls' one-wave kernels handed back so far says nothing
+  // about the new vocabulary: their back-off starts over.
+  m->coop_small_rejects.store(0, std::memory_order_relaxed);
   std::vector<uint8_t> kind(n, 0);
   for (uint64_t i = 0; i < n; ++i) {
     pieces[i].type = types[i];

@@ -876,8 +876,13 @@ class DeviceModel:
 
     def encode_raw_small(self, lines):
         """spm_hip_encode_raw_small_host: raw lines -> final ids (Encode(line,
-        &ids), no extra options) in one launch; None when the fused path does
-        not take the call (SPM_UNIMPLEMENTED)."""
+        &ids), no extra options) in one launch, for 1..16 lines of a unigram
+        or a BPE model; None when the fused path does not take the call
+        (SPM_UNIMPLEMENTED): a line of more than 1024 bytes, raw or (BPE)
+        normalized, a byte-fallback model, a BPE model with USER_DEFINED
+        pieces, a BPE merge that pushes an UNUSED piece, a unigram lattice
+        that needs the general kernel.  After a BPE call stats().coop_rest
+        == n says the kernel ran and handed the call back."""
         buf, off = to_csr(lines)
         n = len(lines)
         cap = int(off[-1]) * 4 + 8 * n + 64
