@@ -482,6 +482,48 @@ int ReserveHostSized(const spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint6
   return SPM_OK;
 }
 
+// ... and its launch: every sentence of the call, no list and no overflow list.
+spm_amd::GeneralLaunch HostSizedLaunch(spm_amd::EncodeWorkspace *ws, const spm_amd::GeneralPool &gp, uint64_t n,
+                                       uint32_t *status, int32_t *s2, uint32_t *s2l) {
+  return spm_amd::GeneralLaunch{nullptr, nullptr, n, ws->w_scratch.as<uint8_t>(), gp.slab, gp.small_nb, gp.lanes,
+                                nullptr, nullptr, status + spm_amd::kStError, s2, s2l, ws->w_ntok.as<uint32_t>()};
+}
+
+// offsets[n] of a device batch (one small copy and wait).
+int BatchBytes(spm_amd::EncodeWorkspace *ws, const uint64_t *d_off, uint64_t n, hipStream_t st, uint64_t *total) {
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 8, d_off + n, 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(total, ws->pinned + 8, 8);
+  if (*total > 0xFFFFFFFFull * 4) return Fail(SPM_OUT_OF_RANGE, "batch too large");
+  return SPM_OK;
+}
+
+int LongestSentence(const uint64_t *d_off, uint64_t n, hipStream_t st, uint32_t *max_nb) {
+  *max_nb = 0;
+  if (n == 0) return SPM_OK;
+  std::vector<uint64_t> off(n + 1);
+  SPM_HIP_TRY(hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipStreamSynchronize(st));
+  for (uint64_t i = 0; i < n; ++i) *max_nb = std::max<uint32_t>(*max_nb, static_cast<uint32_t>(off[i + 1] - off[i]));
+  return SPM_OK;
+}
+
+// The tier counts and kernel times of a blocking call that has been waited
+// for: `flagged` sentences left the fast tier, or all n when the call ran
+// host-sized.  Publishes the call's stats.
+int PublishTierStats(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n, bool host_sized, uint32_t flagged) {
+  ws->stats.sentences = n;
+  ws->stats.general_path = host_sized ? n : flagged;
+  if (m->timing && ws->last_slot >= 0) {
+    const int s = ws->last_slot;
+    if (!host_sized) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.fast_kernel_ms, ws->tev[2 * s], ws->tev[2 * s + 1]));
+    if (ws->stats.general_path) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
+    ws->tcount = 0;  // consumed here; the ring is for the asynchronous entry point
+  }
+  spm_amd::PublishStats(m, ws->stats);
+  return SPM_OK;
+}
+
 // The device-count pass over (list, count): per-lane slabs first, the longer
 // sentences then one at a time with the whole pool.  launch(GeneralLaunch)
 // is the encode or the sample kernel's launcher.
@@ -496,6 +538,61 @@ int LaunchFlaggedPair(spm_amd::EncodeWorkspace *ws, const spm_amd::GeneralPool &
   SPM_HIP_TRY(launch(spm_amd::GeneralLaunch{ovf, novf, 0, scratch, gp.pool, gp.big_nb, 1, nullptr, nullptr, err, s2,
                                             s2l, ntok}));
   return SPM_OK;
+}
+
+// The two tiers of a blocking lattice call (SampleEncode, the entropy, sample
+// and score): fast(status) over every sentence, exact(GeneralLaunch) over the
+// sentences it flagged (device-count passes, no-ops when none was);
+// force_general, or a flagged sentence too long for the device pool, runs
+// the exact tier over every sentence with host-sized scratch.  too_long and
+// broken: the caller's wording of the two failures.  Waits for the kernels
+// and publishes the tier counts; the status words stay in w_ctl.
+template <typename Fast, typename Exact>
+int LatticeTiers(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint64_t *d_off, uint64_t n, uint64_t cap,
+                 int32_t *s2, uint32_t *s2l, const char *too_long, const char *broken, hipStream_t st, Fast fast,
+                 Exact exact) {
+  bool host_sized = m->force_general;
+  uint32_t flagged = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    uint32_t *status = nullptr;
+    int rc = PrepareControl(ws, n, st, &status);
+    if (rc != SPM_OK) return rc;
+    const bool timing = TimedSlot(m, ws) >= 0;
+    spm_amd::GeneralPool gp;
+    if (host_sized) {
+      uint32_t max_nb = 0;
+      rc = LongestSentence(d_off, n, st, &max_nb);
+      if (rc != SPM_OK) return rc;
+      rc = ReserveHostSized(m, ws, n, std::max<uint32_t>(max_nb, 1), too_long, &gp);
+      if (rc != SPM_OK) return rc;
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
+      SPM_HIP_TRY(exact(HostSizedLaunch(ws, gp, n, status, s2, s2l)));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
+    } else {
+      SPM_HIP_TRY(ws->w_flagged.Reserve(n * 4));
+      rc = ReserveGeneralPool(m, ws, n, cap, &gp);
+      if (rc != SPM_OK) return rc;
+      const int slot = ws->last_slot;
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot], st));
+      SPM_HIP_TRY(fast(status));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot + 1], st));
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
+      rc = LaunchFlaggedPair(ws, gp, ws->w_flagged.as<uint32_t>(), status + spm_amd::kStFlagged, status, s2, s2l,
+                             exact);
+      if (rc != SPM_OK) return rc;
+      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
+    }
+    SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, status, 4 * (spm_amd::kStError + 1), hipMemcpyDeviceToHost, st));
+    SPM_HIP_TRY(hipStreamSynchronize(st));
+    flagged = ws->pinned[spm_amd::kStFlagged];
+    const uint32_t err = ws->pinned[spm_amd::kStError];
+    if (err == 0) break;
+    // Bit 0: a flagged sentence outgrew the device pool; anything else is a
+    // broken walk, which a second run would only repeat.
+    if (host_sized || err != 1u) return Fail(SPM_INTERNAL, broken);
+    host_sized = true;
+  }
+  return PublishTierStats(m, ws, n, host_sized, flagged);
 }
 
 // Dense CSR output from the right-aligned slots and w_ntok: LaunchCompact's
@@ -783,9 +880,7 @@ int EncodeUnigramAll(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_a
   uint32_t *s2l = c.len ? ws->w_slot2_len.as<uint32_t>() : nullptr;
   const bool timing = TimedSlot(m, ws) >= 0;
   if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
-  spm_amd::GeneralLaunch g{nullptr, nullptr, n, ws->w_scratch.as<uint8_t>(), gp.slab, gp.small_nb, gp.lanes,
-                           nullptr, nullptr, status + spm_amd::kStError, s2, s2l, ws->w_ntok.as<uint32_t>()};
-  SPM_HIP_TRY(spm_amd::LaunchUnigramGeneral(l, g, st));
+  SPM_HIP_TRY(spm_amd::LaunchUnigramGeneral(l, HostSizedLaunch(ws, gp, n, status, s2, s2l), st));
   if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
   return CompactSlots(ws, c.off, n, s2, s2l, c.ids, c.len, c.tok, status, c.out_status, st);
 }
@@ -892,16 +987,6 @@ int EncodeEnqueue(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd:
   return spm_amd::EncodeBpe(m, ws, c, &g_last_error);
 }
 
-int LongestSentence(const uint64_t *d_off, uint64_t n, hipStream_t st, uint32_t *max_nb) {
-  *max_nb = 0;
-  if (n == 0) return SPM_OK;
-  std::vector<uint64_t> off(n + 1);
-  SPM_HIP_TRY(hipMemcpyAsync(off.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-  SPM_HIP_TRY(hipStreamSynchronize(st));
-  for (uint64_t i = 0; i < n; ++i) *max_nb = std::max<uint32_t>(*max_nb, static_cast<uint32_t>(off[i + 1] - off[i]));
-  return SPM_OK;
-}
-
 // Blocking encode on a leased workspace (spm_hip_encode_batch and the host
 // and SentencePieceText entry points): reads offsets[n], enqueues the
 // encode, waits, and reports the status the reference's Encode would return.
@@ -910,18 +995,12 @@ int LongestSentence(const uint64_t *d_off, uint64_t n, hipStream_t st, uint32_t 
 int EncodeBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *d_bytes, const uint64_t *d_off,
                    uint64_t n, int32_t *d_ids, uint32_t *d_len, uint64_t *d_tok, hipStream_t st) {
   uint64_t total = 0;
-  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 8, d_off + n, 8, hipMemcpyDeviceToHost, st));
-  SPM_HIP_TRY(hipStreamSynchronize(st));
-  std::memcpy(&total, ws->pinned + 8, 8);
-  if (total > 0xFFFFFFFFull * 4) return Fail(SPM_OUT_OF_RANGE, "batch too large");
-  spm_amd::EncodeCall c{d_bytes, d_off, n, total, d_ids, d_len, d_tok, nullptr, st, NeedsHostSized(m), 0};
-  if (c.host_sized) {
-    int rc = LongestSentence(d_off, n, st, &c.max_nb);
-    if (rc != SPM_OK) return rc;
-  }
-  ws->stats = spm_hip_encode_stats{};
-  int rc = EncodeEnqueue(m, ws, c);
+  int rc = BatchBytes(ws, d_off, n, st, &total);
   if (rc != SPM_OK) return rc;
+  spm_amd::EncodeCall c{d_bytes, d_off, n, total, d_ids, d_len, d_tok, nullptr, st, NeedsHostSized(m), 0};
+  if (c.host_sized && (rc = LongestSentence(d_off, n, st, &c.max_nb)) != SPM_OK) return rc;
+  ws->stats = spm_hip_encode_stats{};
+  if ((rc = EncodeEnqueue(m, ws, c)) != SPM_OK) return rc;
   SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, ws->w_ctl.ptr, 4 * (spm_amd::kStCoopRest + 1), hipMemcpyDeviceToHost, st));
   SPM_HIP_TRY(hipStreamSynchronize(st));
   uint32_t flagged = ws->pinned[spm_amd::kStFlagged], err = ws->pinned[spm_amd::kStError];
@@ -936,17 +1015,8 @@ int EncodeBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t
     err = ws->pinned[spm_amd::kStError];
   }
   if (err) return Fail(SPM_INTERNAL, "general encode path: scratch overflow");
-  ws->stats.sentences = n;
-  ws->stats.general_path = c.host_sized ? n : flagged;
   ws->stats.coop_rest = c.host_sized ? 0 : ws->pinned[spm_amd::kStCoopRest];
-  if (m->timing && ws->last_slot >= 0) {
-    const int s = ws->last_slot;
-    if (!c.host_sized) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.fast_kernel_ms, ws->tev[2 * s], ws->tev[2 * s + 1]));
-    if (ws->stats.general_path) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
-    ws->tcount = 0;  // consumed here; the ring is for the asynchronous entry point
-  }
-  spm_amd::PublishStats(m, ws->stats);
-  return SPM_OK;
+  return PublishTierStats(m, ws, n, c.host_sized, flagged);
 }
 
 // Lazy device tables of the normalizer (charsmap blob, user-defined trie).
@@ -2555,19 +2625,14 @@ int EncodeHostSmall(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_
   return rc;
 }
 
-// Blocking SampleEncode on a leased workspace: the fast tier over every
-// sentence, the exact tier over the sentences it flagged (device-count
-// passes, no-ops when none was), then scan + compaction.  force_general, or
-// a flagged sentence too long for the device pool, runs the exact tier over
-// every sentence with host-sized scratch.
+// Blocking SampleEncode on a leased workspace: LatticeTiers' two tiers leave
+// the draws in the right-aligned slots, then scan + compaction.
 int SampleBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *d_bytes, const uint64_t *d_off,
                    uint64_t n, float theta, uint64_t seed, uint64_t index_base, int32_t *d_ids, uint32_t *d_len,
                    uint64_t *d_tok, hipStream_t st) {
   uint64_t total = 0;
-  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 8, d_off + n, 8, hipMemcpyDeviceToHost, st));
-  SPM_HIP_TRY(hipStreamSynchronize(st));
-  std::memcpy(&total, ws->pinned + 8, 8);
-  if (total > 0xFFFFFFFFull * 4) return Fail(SPM_OUT_OF_RANGE, "batch too large");
+  int rc = BatchBytes(ws, d_off, n, st, &total);
+  if (rc != SPM_OK) return rc;
   ws->stats = spm_hip_encode_stats{};
   if (n == 0) {
     SPM_HIP_TRY(hipMemsetAsync(d_tok, 0, sizeof(uint64_t), st));
@@ -2581,81 +2646,32 @@ int SampleBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t
   SPM_HIP_TRY(ws->w_ntok.Reserve(n * 4));
   int32_t *s2 = ws->w_slot2_ids.as<int32_t>();
   uint32_t *s2l = d_len ? ws->w_slot2_len.as<uint32_t>() : nullptr;
-  uint32_t *ntok = ws->w_ntok.as<uint32_t>();
   const uint32_t num_units = static_cast<uint32_t>(m->trie.units.size());
-  bool host_sized = m->force_general;
-  uint32_t flagged = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    uint32_t *status = nullptr;
-    int rc = PrepareControl(ws, n, st, &status);
-    if (rc != SPM_OK) return rc;
-    // The exact tier over the sentences of g (SampleExactArgs ends with GeneralLaunch's fields).
-    auto exact = [&](const spm_amd::GeneralLaunch &g) {
-      const spm_amd::SampleExactArgs x{d_bytes, d_off, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
-                                       m->d_scores.as<float>(), num_units, m->up, theta, seed, index_base,
-                                       g.slot_ids, g.slot_len, g.ntok, g.list, g.count, g.list_n, g.scratch,
-                                       g.slab_bytes, g.max_nb, g.ovf_list, g.ovf_count, g.error, g.threads};
-      return spm_amd::LaunchUnigramSampleExact(x, st);
-    };
-    const bool timing = TimedSlot(m, ws) >= 0;
-    if (host_sized) {
-      uint32_t max_nb = 0;
-      rc = LongestSentence(d_off, n, st, &max_nb);
-      if (rc != SPM_OK) return rc;
-      spm_amd::GeneralPool gp;
-      rc = ReserveHostSized(m, ws, n, std::max<uint32_t>(max_nb, 1), "sentence too long for the exact sampling path",
-                            &gp);
-      if (rc != SPM_OK) return rc;
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
-      SPM_HIP_TRY(exact(spm_amd::GeneralLaunch{nullptr, nullptr, n, ws->w_scratch.as<uint8_t>(), gp.slab, gp.small_nb,
-                                               gp.lanes, nullptr, nullptr, status + spm_amd::kStError, s2, s2l,
-                                               ntok}));
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
-    } else {
-      SPM_HIP_TRY(ws->w_salpha.Reserve((cap + n + 1) * 4));
-      SPM_HIP_TRY(ws->w_smask.Reserve((cap + n + 1) * 8));
-      SPM_HIP_TRY(ws->w_flagged.Reserve(n * 4));
-      spm_amd::GeneralPool gp;
-      rc = ReserveGeneralPool(m, ws, n, cap, &gp);
-      if (rc != SPM_OK) return rc;
-      spm_amd::SampleFastArgs f{d_bytes, d_off, n, total, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
-                                m->d_scores.as<float>(), num_units, m->up, theta, seed, index_base,
-                                ws->w_salpha.as<float>(), ws->w_smask.as<uint64_t>(), s2, s2l, ntok,
-                                ws->w_flagged.as<uint32_t>(), status};
-      const int slot = ws->last_slot;
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot], st));
-      SPM_HIP_TRY(spm_amd::LaunchUnigramSampleFast(f, st));
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot + 1], st));
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
-      rc = LaunchFlaggedPair(ws, gp, ws->w_flagged.as<uint32_t>(), status + spm_amd::kStFlagged, status, s2, s2l,
-                             exact);
-      if (rc != SPM_OK) return rc;
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
-    }
-    SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, status, 4 * (spm_amd::kStError + 1), hipMemcpyDeviceToHost, st));
-    SPM_HIP_TRY(hipStreamSynchronize(st));
-    flagged = ws->pinned[spm_amd::kStFlagged];
-    const uint32_t err = ws->pinned[spm_amd::kStError];
-    if (err == 0) {
-      rc = CompactSlots(ws, d_off, n, s2, s2l, d_ids, d_len, d_tok, status, nullptr, st);
-      if (rc != SPM_OK) return rc;
-      SPM_HIP_TRY(hipStreamSynchronize(st));
-      break;
-    }
-    // Bit 0: a flagged sentence outgrew the device pool; anything else is a
-    // broken walk, which a second run would only repeat.
-    if (host_sized || err != 1u) return Fail(SPM_INTERNAL, "exact sampling path: scratch overflow or broken walk");
-    host_sized = true;
+  if (!m->force_general) {
+    SPM_HIP_TRY(ws->w_salpha.Reserve((cap + n + 1) * 4));
+    SPM_HIP_TRY(ws->w_smask.Reserve((cap + n + 1) * 8));
   }
-  ws->stats.sentences = n;
-  ws->stats.general_path = host_sized ? n : flagged;
-  if (m->timing && ws->last_slot >= 0) {
-    const int s = ws->last_slot;
-    if (!host_sized) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.fast_kernel_ms, ws->tev[2 * s], ws->tev[2 * s + 1]));
-    if (ws->stats.general_path) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
-    ws->tcount = 0;
-  }
-  spm_amd::PublishStats(m, ws->stats);
+  auto fast = [&](uint32_t *status) {
+    const spm_amd::SampleFastArgs f{d_bytes, d_off, n, total, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                                    m->d_scores.as<float>(), num_units, m->up, theta, seed, index_base,
+                                    ws->w_salpha.as<float>(), ws->w_smask.as<uint64_t>(), s2, s2l,
+                                    ws->w_ntok.as<uint32_t>(), ws->w_flagged.as<uint32_t>(), status};
+    return spm_amd::LaunchUnigramSampleFast(f, st);
+  };
+  // The exact tier over the sentences of g (SampleExactArgs ends with GeneralLaunch's fields).
+  auto exact = [&](const spm_amd::GeneralLaunch &g) {
+    const spm_amd::SampleExactArgs x{d_bytes, d_off, m->d_units.as<uint32_t>(), m->d_values.as<int32_t>(),
+                                     m->d_scores.as<float>(), num_units, m->up, theta, seed, index_base,
+                                     g.slot_ids, g.slot_len, g.ntok, g.list, g.count, g.list_n, g.scratch,
+                                     g.slab_bytes, g.max_nb, g.ovf_list, g.ovf_count, g.error, g.threads};
+    return spm_amd::LaunchUnigramSampleExact(x, st);
+  };
+  rc = LatticeTiers(m, ws, d_off, n, cap, s2, s2l, "sentence too long for the exact sampling path",
+                    "exact sampling path: scratch overflow or broken walk", st, fast, exact);
+  if (rc != SPM_OK) return rc;
+  rc = CompactSlots(ws, d_off, n, s2, s2l, d_ids, d_len, d_tok, ws->w_ctl.as<uint32_t>(), nullptr, st);
+  if (rc != SPM_OK) return rc;
+  SPM_HIP_TRY(hipStreamSynchronize(st));
   return SPM_OK;
 }
 
@@ -2667,17 +2683,33 @@ int SampleArgsCheck(const spm_hip_model *m, float theta) {
   return SPM_OK;
 }
 
-// Host batch entry points: the workspace's device copies of the input
-// (h_in, h_off) uploaded and its output buffers (h_ids, h_len, h_tok) sized.
-int StageHostBatch(spm_amd::EncodeWorkspace *ws, const uint8_t *bytes, const uint64_t *off, uint64_t n,
-                   uint64_t total, bool with_len, hipStream_t st) {
+// Host batch entry points: offsets that start at 0 and never decrease.
+int HostOffsetsCheck(const uint64_t *off, uint64_t n) {
+  if (off[0] != 0) return Fail(SPM_INVALID_ARGUMENT, "offsets must start at 0");
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
+  return SPM_OK;
+}
+
+// The workspace's device copies of a host batch (h_in, h_off), uploaded.
+int StageHostInput(spm_amd::EncodeWorkspace *ws, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                   uint64_t total, hipStream_t st) {
   SPM_HIP_TRY(ws->h_in.Reserve(std::max<uint64_t>(total, 1)));
   SPM_HIP_TRY(ws->h_off.Reserve((n + 1) * 8));
+  if (total) SPM_HIP_TRY(hipMemcpyAsync(ws->h_in.ptr, bytes, total, hipMemcpyHostToDevice, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->h_off.ptr, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  return SPM_OK;
+}
+
+// ... and the output buffers of an encode or a SampleEncode (h_ids, h_len,
+// h_tok) sized.
+int StageHostBatch(spm_amd::EncodeWorkspace *ws, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                   uint64_t total, bool with_len, hipStream_t st) {
+  const int rc = StageHostInput(ws, bytes, off, n, total, st);
+  if (rc != SPM_OK) return rc;
   SPM_HIP_TRY(ws->h_ids.Reserve(std::max<uint64_t>(total, 1) * 4));
   if (with_len) SPM_HIP_TRY(ws->h_len.Reserve(std::max<uint64_t>(total, 1) * 4));
   SPM_HIP_TRY(ws->h_tok.Reserve((n + 1) * 8));
-  if (total) SPM_HIP_TRY(hipMemcpyAsync(ws->h_in.ptr, bytes, total, hipMemcpyHostToDevice, st));
-  SPM_HIP_TRY(hipMemcpyAsync(ws->h_off.ptr, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
   return SPM_OK;
 }
 
@@ -3053,9 +3085,7 @@ int spm_hip_sample_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, con
   int rc = SampleArgsCheck(m, theta);
   if (rc != SPM_OK) return rc;
   if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
-  if (off[0] != 0) return Fail(SPM_INVALID_ARGUMENT, "offsets must start at 0");
-  for (uint64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
+  if ((rc = HostOffsetsCheck(off, n)) != SPM_OK) return rc;
   const uint64_t total = off[n];
   if (total && (!bytes || !ids)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
   spm_amd::WorkspaceLease ws;
@@ -3073,7 +3103,6 @@ int spm_hip_sample_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, con
 // ---------------------------------------------------------------------------
 // Lattice scores (unigram_lattice_score.hip): CalculateEntropy and
 // SampleEncodeAndScore.
-extern "C++" {  // (LatticeTiers is a template)
 namespace {
 
 int LatticeScoreArgsCheck(const spm_hip_model *m, float theta, const char *what) {
@@ -3081,86 +3110,6 @@ int LatticeScoreArgsCheck(const spm_hip_model *m, float theta, const char *what)
   if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
   if (m->model_type != spm_amd::kUnigram)
     return Fail(SPM_UNIMPLEMENTED, std::string(what) + " is implemented for unigram models only");
-  return SPM_OK;
-}
-
-int HostOffsetsCheck(const uint64_t *off, uint64_t n) {
-  if (off[0] != 0) return Fail(SPM_INVALID_ARGUMENT, "offsets must start at 0");
-  for (uint64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
-  return SPM_OK;
-}
-
-// The two tiers of a lattice-score call, SampleBlocking's plan: fast(status)
-// over every sentence, exact(GeneralLaunch) over the sentences it flagged
-// (device-count passes); force_general, or a flagged sentence too long for
-// the device pool, runs the exact tier over every sentence with host-sized
-// scratch.  Waits for the kernels and publishes the tier counts.
-template <typename Fast, typename Exact>
-int LatticeTiers(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint64_t *d_off, uint64_t n, uint64_t cap,
-                 int32_t *s2, uint32_t *s2l, const char *too_long, hipStream_t st, Fast fast, Exact exact) {
-  bool host_sized = m->force_general;
-  uint32_t flagged = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    uint32_t *status = nullptr;
-    int rc = PrepareControl(ws, n, st, &status);
-    if (rc != SPM_OK) return rc;
-    const bool timing = TimedSlot(m, ws) >= 0;
-    if (host_sized) {
-      uint32_t max_nb = 0;
-      rc = LongestSentence(d_off, n, st, &max_nb);
-      if (rc != SPM_OK) return rc;
-      spm_amd::GeneralPool gp;
-      rc = ReserveHostSized(m, ws, n, std::max<uint32_t>(max_nb, 1), too_long, &gp);
-      if (rc != SPM_OK) return rc;
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
-      SPM_HIP_TRY(exact(spm_amd::GeneralLaunch{nullptr, nullptr, n, ws->w_scratch.as<uint8_t>(), gp.slab, gp.small_nb,
-                                               gp.lanes, nullptr, nullptr, status + spm_amd::kStError, s2, s2l,
-                                               ws->w_ntok.as<uint32_t>()}));
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
-    } else {
-      SPM_HIP_TRY(ws->w_flagged.Reserve(n * 4));
-      spm_amd::GeneralPool gp;
-      rc = ReserveGeneralPool(m, ws, n, cap, &gp);
-      if (rc != SPM_OK) return rc;
-      const int slot = ws->last_slot;
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot], st));
-      SPM_HIP_TRY(fast(status));
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->tev[2 * slot + 1], st));
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[0], st));
-      rc = LaunchFlaggedPair(ws, gp, ws->w_flagged.as<uint32_t>(), status + spm_amd::kStFlagged, status, s2, s2l,
-                             exact);
-      if (rc != SPM_OK) return rc;
-      if (timing) SPM_HIP_TRY(hipEventRecord(ws->ev[1], st));
-    }
-    SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, status, 4 * (spm_amd::kStError + 1), hipMemcpyDeviceToHost, st));
-    SPM_HIP_TRY(hipStreamSynchronize(st));
-    flagged = ws->pinned[spm_amd::kStFlagged];
-    const uint32_t err = ws->pinned[spm_amd::kStError];
-    if (err == 0) break;
-    // Bit 0: a flagged sentence outgrew the device pool; anything else is a
-    // broken walk, which a second run would only repeat.
-    if (host_sized || err != 1u) return Fail(SPM_INTERNAL, "exact lattice path: scratch overflow or broken walk");
-    host_sized = true;
-  }
-  ws->stats.sentences = n;
-  ws->stats.general_path = host_sized ? n : flagged;
-  if (m->timing && ws->last_slot >= 0) {
-    const int s = ws->last_slot;
-    if (!host_sized) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.fast_kernel_ms, ws->tev[2 * s], ws->tev[2 * s + 1]));
-    if (ws->stats.general_path) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
-    ws->tcount = 0;
-  }
-  spm_amd::PublishStats(m, ws->stats);
-  return SPM_OK;
-}
-
-// offsets[n] of a device batch (one small copy and wait).
-int BatchBytes(spm_amd::EncodeWorkspace *ws, const uint64_t *d_off, uint64_t n, hipStream_t st, uint64_t *total) {
-  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned + 8, d_off + n, 8, hipMemcpyDeviceToHost, st));
-  SPM_HIP_TRY(hipStreamSynchronize(st));
-  std::memcpy(total, ws->pinned + 8, 8);
-  if (*total > 0xFFFFFFFFull * 4) return Fail(SPM_OUT_OF_RANGE, "batch too large");
   return SPM_OK;
 }
 
@@ -3194,8 +3143,8 @@ int EntropyBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_
                                       g.error, g.threads};
     return spm_amd::LaunchUnigramEntropyExact(x, st);
   };
-  return LatticeTiers(m, ws, d_off, n, cap, nullptr, nullptr, "sentence too long for the exact entropy path", st,
-                      fast, exact);
+  return LatticeTiers(m, ws, d_off, n, cap, nullptr, nullptr, "sentence too long for the exact entropy path",
+                      "exact lattice path: scratch overflow or broken walk", st, fast, exact);
 }
 
 // Sample and score on a leased workspace: the rows' token offsets go to
@@ -3246,7 +3195,8 @@ int ScoreBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t 
         ns, d_scores};
     return spm_amd::LaunchUnigramScoreExact(x, st);
   };
-  rc = LatticeTiers(m, ws, d_off, n, cap, s2, s2l, "sentence too long for the exact sampling path", st, fast, exact);
+  rc = LatticeTiers(m, ws, d_off, n, cap, s2, s2l, "sentence too long for the exact sampling path",
+                    "exact lattice path: scratch overflow or broken walk", st, fast, exact);
   if (rc != SPM_OK) return rc;
   size_t tmp = 0;
   SPM_HIP_TRY(spm_amd::LaunchScoreScan(ws->w_ntok.as<uint32_t>(), rows, d_tok, nullptr, &tmp, st));
@@ -3277,7 +3227,6 @@ int ScoreArgsCheck(const spm_hip_model *m, uint64_t n, uint32_t ns, float theta)
 }
 
 }  // namespace
-}  // extern "C++"
 
 int spm_hip_entropy_batch(spm_hip_model *m, const uint8_t *d_bytes, const uint64_t *d_off, uint64_t n, float theta,
                           float *d_entropy, float *d_log_z, void *stream) {
@@ -3305,12 +3254,9 @@ int spm_hip_entropy_batch_host(spm_hip_model *m, const uint8_t *bytes, const uin
   spm_amd::WorkspaceLease ws;
   SPM_LEASE(ws, ws.ForHost(m));
   hipStream_t st = ws.stream();
-  SPM_HIP_TRY(ws->h_in.Reserve(std::max<uint64_t>(total, 1)));
-  SPM_HIP_TRY(ws->h_off.Reserve((n + 1) * 8));
   SPM_HIP_TRY(ws->w_lscore.Reserve(std::max<uint64_t>(n, 1) * 4));
   if (log_z) SPM_HIP_TRY(ws->w_llogz.Reserve(std::max<uint64_t>(n, 1) * 4));
-  if (total) SPM_HIP_TRY(hipMemcpyAsync(ws->h_in.ptr, bytes, total, hipMemcpyHostToDevice, st));
-  SPM_HIP_TRY(hipMemcpyAsync(ws->h_off.ptr, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  if ((rc = StageHostInput(ws.get(), bytes, off, n, total, st)) != SPM_OK) return rc;
   rc = EntropyBlocking(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), n, theta,
                        ws->w_lscore.as<float>(), log_z ? ws->w_llogz.as<float>() : nullptr, st);
   if (rc != SPM_OK || n == 0) return rc;
@@ -3359,12 +3305,9 @@ int spm_hip_sample_encode_and_score_batch_host(spm_hip_model *m, const uint8_t *
   spm_amd::WorkspaceLease ws;
   SPM_LEASE(ws, ws.ForHost(m));
   hipStream_t st = ws.stream();
-  SPM_HIP_TRY(ws->h_in.Reserve(std::max<uint64_t>(total, 1)));
-  SPM_HIP_TRY(ws->h_off.Reserve((n + 1) * 8));
   SPM_HIP_TRY(ws->h_tok.Reserve((rows + 1) * 8));
   SPM_HIP_TRY(ws->w_lscore.Reserve(std::max<uint64_t>(rows, 1) * 4));
-  if (total) SPM_HIP_TRY(hipMemcpyAsync(ws->h_in.ptr, bytes, total, hipMemcpyHostToDevice, st));
-  SPM_HIP_TRY(hipMemcpyAsync(ws->h_off.ptr, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  if ((rc = StageHostInput(ws.get(), bytes, off, n, total, st)) != SPM_OK) return rc;
   uint64_t T = 0;
   rc = ScoreBlocking(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), n, num_samples, theta, seed,
                      index_base, len != nullptr, ws->h_tok.as<uint64_t>(), ws->w_lscore.as<float>(), &T, st);
@@ -3430,19 +3373,14 @@ int spm_hip_nbest_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, cons
   int rc = NBestArgsCheck(m);
   if (rc != SPM_OK) return rc;
   if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
-  if (off[0] != 0) return Fail(SPM_INVALID_ARGUMENT, "offsets must start at 0");
-  for (uint64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return Fail(SPM_INVALID_ARGUMENT, "offsets must not decrease");
+  if ((rc = HostOffsetsCheck(off, n)) != SPM_OK) return rc;
   const uint64_t total = off[n];
   if (total && !bytes) return Fail(SPM_INVALID_ARGUMENT, "null argument");
   const int N = spm_amd::NBestClamp(nbest_size);
   spm_amd::WorkspaceLease ws;
   SPM_LEASE(ws, ws.ForHost(m));
   hipStream_t st = ws.stream();
-  SPM_HIP_TRY(ws->h_in.Reserve(std::max<uint64_t>(total, 1)));
-  SPM_HIP_TRY(ws->h_off.Reserve((n + 1) * 8));
-  if (total) SPM_HIP_TRY(hipMemcpyAsync(ws->h_in.ptr, bytes, total, hipMemcpyHostToDevice, st));
-  SPM_HIP_TRY(hipMemcpyAsync(ws->h_off.ptr, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  if ((rc = StageHostInput(ws.get(), bytes, off, n, total, st)) != SPM_OK) return rc;
   uint64_t P = 0, T = 0;
   rc = NBestSearch(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), bytes, n, N, len != nullptr, &P, &T,
                    st);

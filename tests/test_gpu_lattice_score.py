@@ -6,6 +6,7 @@ lattice_score_selftest."""
 import math
 import os
 import subprocess
+import time
 
 import numpy as np
 import pytest
@@ -18,6 +19,7 @@ import sample_ref as R
 import spm_amd as S
 import vocab_ref
 from model_builder import NORMAL, UNIGRAM, UNUSED, USER_DEFINED, model
+from test_gpu_sample import _edge_model as sample_edge_model, _rows as sample_rows
 from test_lattice_score_cpu import MAX_DIFFERING, REL_BOUND, rel_dev
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -219,6 +221,73 @@ def test_edge_leaf_inside_char():
     general = _check_edges(mb, sents, (THETA,))
     assert general[("entropy", False)] == 3 and general[("score", False)] == 3
     assert general[("entropy", False)] > 0
+
+
+RERUN_BYTES = 264000  # above the largest slab of any device pool (262 144 + floor(127 * 140 / A) <= 262 514)
+
+
+def _rerun_batch(norm, p70):
+    """Three short sentences that every fast tier keeps (no "▁": the entropy
+    case's model flags that char), then one of RERUN_BYTES bytes that holds
+    the 70-byte piece once, between two whole words of running text."""
+    sp = "▁".encode()
+    text = b"".join(norm) * (RERUN_BYTES // sum(len(s) for s in norm) + 1)
+    cut1 = text.rfind(sp, 0, RERUN_BYTES // 2)
+    cut2 = text.rfind(sp, 0, RERUN_BYTES - len(p70))
+    long = text[:cut1] + p70 + text[cut1:cut2]
+    long += b"a" * (RERUN_BYTES - len(long))
+    assert len(long) == RERUN_BYTES and long.count(p70) == 1
+    return [b"hello", b"a", b"thequickbrownfox", long]
+
+
+def _rerun_call(call, dm, sents):
+    """The call's outputs by sentence, and every float among them."""
+    buf, off = S.to_csr(sents)
+    if call == "sample_encode_csr_host":
+        rows = sample_rows(*dm.sample_encode_csr_host(buf, off, THETA, SEED, with_lens=True))
+        return rows, np.zeros(0, F32)
+    if call == "entropy_csr_host":
+        h, z = dm.entropy_csr_host(buf, off, THETA, with_log_z=True)
+        return list(zip(_bits(h).tolist(), _bits(z).tolist())), np.concatenate([h, z])
+    ids, to, sc, lens = dm.sample_encode_and_score_csr_host(buf, off, 2, THETA, SEED, with_lens=True)
+    rows = _rows(ids, to, sc, lens)
+    return [rows[2 * i:2 * i + 2] for i in range(len(sents))], sc
+
+
+@pytest.mark.parametrize("call", ["sample_encode_csr_host", "entropy_csr_host", "sample_encode_and_score_csr_host"])
+def test_exact_tier_rerun_host_sized(call):
+    """A flagged sentence longer than the device pool's largest slab: the
+    call runs again with host-sized scratch over the whole batch.  The short
+    sentences get what a call of them alone gives, the long one what the call
+    gives under set_force_general, bit for bit.
+
+    The model is test_gpu_sample.py's edge model.  The sampler's fast tier
+    (SampleEncode and SampleEncodeAndScore) flags the walk over the 70-byte
+    piece.  The entropy's fast tier has no 64-byte limit (test_edge_sentences)
+    and flags only a trie leaf inside a UTF-8 char, so its case takes the edge
+    model with the piece that ends inside "▁": with the plain one the long
+    sentence stays in the fast tier and nothing runs again."""
+    mb, _, p70 = sample_edge_model(half=call == "entropy_csr_host")
+    dm = S.DeviceModel(mb)
+    sents = _rerun_batch(fixture_data("botchan_test_model")[2], p70)
+    t0 = time.perf_counter()
+    got, floats = _rerun_call(call, dm, sents)
+    t1 = time.perf_counter()
+    assert dm.stats().general_path == 4
+    short, _ = _rerun_call(call, dm, sents[:3])
+    assert dm.stats().general_path == 0
+    dm.set_force_general(True)
+    try:
+        t2 = time.perf_counter()
+        forced, _ = _rerun_call(call, dm, sents)
+        t3 = time.perf_counter()
+    finally:
+        dm.set_force_general(False)
+    print("%s: call with the re-run %.2f s, forced call %.2f s" % (call, t1 - t0, t3 - t2))
+    assert len(got) == 4
+    assert got[:3] == short
+    assert got[3] == forced[3]
+    assert np.isfinite(floats).all()
 
 
 def test_restricted_vocabulary():
