@@ -240,6 +240,56 @@ int spm_hip_sample_encode_batch_host(spm_hip_model *model, const uint8_t *norm_b
  * `seed`, the stream above (*u in [0, 1), a multiple of 2^-53). */
 int spm_hip_sample_uniform(uint64_t seed, uint64_t index, uint64_t draw, double *u);
 
+/* BPE-dropout: batched SampleEncode of a BPE model, as bpe::Model::SampleEncode
+ * of the `sentencepiece` package (0.2.x, bpe_model.cc) does it.  Arguments,
+ * capacity, layout and d_piece_len are those of spm_hip_sample_encode_batch;
+ * one draw per sentence.  (The vendored v0.1.82 reference has no BPE sampling.)
+ *
+ * The rule: the merge loop of Encode pops the agenda in order (score
+ * descending, left index ascending), discards stale entries, and then drops
+ * the popped pair for good with probability alpha, else merges it.  The
+ * initial split, the user-defined freeze, rev_merge and the resegmentation of
+ * UNUSED pieces are those of Encode.  alpha <= 0 never drops (the result is
+ * Encode's), alpha >= 1 always drops (one token per initial symbol); values
+ * outside [0, 1], the infinities included, clamp.
+ *
+ * Random stream: spm_hip_sample_encode_batch's, one decision per pair, named
+ * by the pair's bytes.  With start = the offset of the left symbol's first
+ * byte in the normalized sentence and end = the offset one past the right
+ * symbol's last byte (symbols only grow, so no (start, end) is offered twice
+ * in one sentence), sentence i of a call (g = index_base + i) drops the pair
+ * when
+ *   spm_hip_sample_uniform(seed, g, ((uint64_t) start << 32) | end, &u),
+ *   u < (double) alpha,
+ * which the kernels test as (mix(..) >> 11) < ceil((double) alpha * 2^53)
+ * (spm_hip_bpe_dropout_threshold).  A result depends on (seed, g, sentence,
+ * alpha) only: not on the batch, the kernel that ran the sentence or the
+ * launch geometry.  The package draws from a process-wide mt19937; what is
+ * kept is the distribution.
+ *
+ * Status: NaN alpha -> SPM_INVALID_ARGUMENT.  A model that is not BPE ->
+ * SPM_UNIMPLEMENTED (unigram models sample with
+ * spm_hip_sample_encode_batch, which in turn keeps answering
+ * SPM_UNIMPLEMENTED for BPE models).  A host-only handle ->
+ * SPM_FAILED_PRECONDITION.  n = 0 is fine.  spm_hip_model_last_stats reports
+ * general_path = the sentences the literal kernel took: sentences of more
+ * than 1024 bytes, those that probe an UNUSED piece or (models whose pieces
+ * do not all split into pieces) hold a char outside the vocabulary, every
+ * sentence of a model with USER_DEFINED pieces or under
+ * spm_hip_model_set_force_general; both kernels give the same result. */
+int spm_hip_bpe_dropout_encode_batch(spm_hip_model *model, const uint8_t *d_norm_bytes,
+                                     const uint64_t *d_offsets, uint64_t n, float alpha, uint64_t seed,
+                                     uint64_t index_base, int32_t *d_ids, uint32_t *d_piece_len,
+                                     uint64_t *d_tok_offsets, void *stream);
+/* Same contract with HOST buffers (offsets start at 0). */
+int spm_hip_bpe_dropout_encode_batch_host(spm_hip_model *model, const uint8_t *norm_bytes,
+                                          const uint64_t *offsets, uint64_t n, float alpha, uint64_t seed,
+                                          uint64_t index_base, int32_t *ids, uint32_t *piece_len,
+                                          uint64_t *tok_offsets);
+/* Host only: the integer threshold of alpha, ceil((double) alpha * 2^53)
+ * clamped to [0, 2^53].  NaN -> SPM_INVALID_ARGUMENT. */
+int spm_hip_bpe_dropout_threshold(float alpha, uint64_t *threshold);
+
 /* Batched SentencePieceProcessor::CalculateEntropy of the `sentencepiece`
  * package (0.2.x): the entropy of every sentence's segmentation distribution
  * at inverse temperature theta, DEVICE pointers, unigram models.

@@ -8,6 +8,8 @@
 
 #include <cstdint>
 
+#include "sample_rng.h"
+
 namespace spm_amd {
 namespace {
 
@@ -74,6 +76,15 @@ __device__ __forceinline__ int32_t ExactEntry(const BpeArgs &a, const uint8_t *s
   return (len && (u & 0x100u)) ? a.values[node] : -1;
 }
 
+// Hands sentence i (nb bytes) to the general kernel: status[0] counts the
+// flagged sentences, status[1] keeps the longest.
+__device__ __forceinline__ void FlagSentence(const BpeArgs &a, uint64_t i, uint32_t nb) {
+  a.ntok[i] = 0xFFFFFFFFu;
+  const uint32_t k = atomicAdd(&a.status[0], 1u);
+  a.flagged[k] = static_cast<uint32_t>(i);
+  atomicMax(&a.status[1], nb);
+}
+
 // One 16-byte load per probe returns the merged id, its score and whether it
 // is UNUSED (the fast kernel's per-merge dependent chain is this load alone).
 __device__ __forceinline__ int32_t PairLookupFused(const BpeArgs &a, int32_t l, int32_t r, uint32_t *rank,
@@ -92,6 +103,19 @@ __device__ __forceinline__ int32_t PairLookupFused(const BpeArgs &a, int32_t l, 
     if (e.x == 0xFFFFFFFFu && e.y == 0xFFFFFFFFu) return -1;
     h = (h + 1) & mask;
   }
+}
+
+// BPE-dropout of one sentence: its key in the sampler's counter-based stream
+// (SampleKey(seed, global index)) and the integer threshold ceil(alpha * 2^53).
+struct BpeDropKey {
+  uint64_t key, threshold;
+};
+
+// The pair named (start, end) is dropped: SampleDraw(key, start << 32 | end)
+// < alpha, as an integer compare (the draw is (mix >> 11) * 2^-53).
+__device__ __forceinline__ bool BpeDropped(const BpeDropKey &d, uint32_t start, uint32_t end) {
+  const uint64_t k = (static_cast<uint64_t>(start) << 32) | end;
+  return (SampleMix(d.key + kSampleGolden * (k + 1)) >> 11) < d.threshold;
 }
 
 // Pair keys: the entry's w word is the merged piece's score as a dense rank

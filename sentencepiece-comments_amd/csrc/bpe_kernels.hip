@@ -86,13 +86,6 @@ __device__ __forceinline__ int32_t PairLookup(const BpeArgs &a, int32_t l, int32
 
 __device__ __forceinline__ int32_t ReadLane(int32_t v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 
-__device__ __forceinline__ void FlagSentence(const BpeArgs &a, uint64_t i, uint32_t nb) {
-  a.ntok[i] = 0xFFFFFFFFu;
-  const uint32_t k = atomicAdd(&a.status[0], 1u);
-  a.flagged[k] = static_cast<uint32_t>(i);
-  atomicMax(&a.status[1], nb);
-}
-
 // LDS hand-off between the lanes of ONE wavefront (the half kernel's loop
 // trip count is per wave, so a block barrier would not be uniform).
 __device__ __forceinline__ void WaveSync() {
@@ -921,6 +914,9 @@ struct GenBpeArgs {
   uint32_t *__restrict__ ovf_list;    // sentences longer than max_nb (nullptr: error)
   uint32_t *__restrict__ ovf_count;
   uint32_t lanes;                     // slabs in scratch
+  // bpe_general_kernel<true> (BPE-dropout): ceil(alpha * 2^53) and the draw
+  // stream of sentence i, SampleKey(seed, index_base + i).
+  uint64_t drop_threshold, drop_seed, drop_index_base;
 };
 
 // comparator of bpe_model.cc:55-61: true if h1 has LOWER priority than h2.
@@ -928,6 +924,10 @@ __device__ __forceinline__ bool Lower(const PairRec &h1, const PairRec &h2) {
   return h1.score < h2.score || (h1.score == h2.score && h1.left > h2.left);
 }
 
+// kDrop: BPE-dropout (bpe::Model::SampleEncode of the sentencepiece package):
+// a popped pair that passes the stale check is dropped for good when its draw
+// is below alpha; the draw is named by the pair's bytes (BpeDropped).
+template <bool kDrop>
 __global__ __launch_bounds__(64) void bpe_general_kernel(GenBpeArgs g) {
   const BpeArgs &a = g.a;
   const uint64_t tid = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -965,6 +965,8 @@ __global__ __launch_bounds__(64) void bpe_general_kernel(GenBpeArgs g) {
     uint32_t *rev_left = reinterpret_cast<uint32_t *>(rev_piece + cap);
     uint32_t *stk = rev_left + cap;  // (off, len) pairs, 2*nb entries each
     int32_t npool = 0, nheap = 0, nrev = 0;
+    BpeDropKey drop{};
+    if constexpr (kDrop) drop = BpeDropKey{SampleKey(g.drop_seed, g.drop_index_base + i), g.drop_threshold};
 
     auto heap_push = [&](int32_t r) {
       int32_t c = nheap++;
@@ -1051,6 +1053,9 @@ __global__ __launch_bounds__(64) void bpe_general_kernel(GenBpeArgs g) {
       if (slen[top.left] == 0 || slen[top.right] == 0 ||
           slen[top.left] + slen[top.right] != top.size)
         continue;
+      if constexpr (kDrop) {
+        if (BpeDropped(drop, soff[top.left], soff[top.right] + slen[top.right])) continue;
+      }
       slen[top.left] += slen[top.right];
       snext[top.left] = snext[top.right];
       if (snext[top.right] >= 0) sprev[snext[top.right]] = top.left;
@@ -1362,6 +1367,8 @@ hipError_t LaunchBpeCompact(const uint64_t *off, uint64_t n, const uint32_t *nto
 // for longer sentences), scan + compaction.  No host synchronization unless
 // c.host_sized (general kernel over every sentence, scratch sized from the
 // longest sentence: models with user-defined symbols, force_general).
+// c.drop (BPE-dropout): bpe_dropout_kernel (bpe_dropout.hip) in place of the
+// lane / half / fast kernels and bpe_general_kernel<true> for what it flags.
 int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::string *err) {
 #define BPE_TRY(expr)                                              \
   do {                                                             \
@@ -1395,6 +1402,17 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
     return e ? std::atoi(e) : 1;
   }();
   a.pipe_probes = kPipeProbes;
+  // A/B knob: SPM_HIP_BPE_FAST_ONLY=1 runs bpe_fast_kernel alone (one sentence
+  // per wave over the whole batch), the yardstick of the dropout wave kernel.
+  static const bool kFastOnly = [] {
+    const char *e = std::getenv("SPM_HIP_BPE_FAST_ONLY");
+    return e && std::atoi(e) != 0;
+  }();
+  const BpeDropout drop = c.drop ? *c.drop : BpeDropout{};
+  auto general = [&](dim3 grid, const GenBpeArgs &g) {
+    if (c.drop) hipLaunchKernelGGL(bpe_general_kernel<true>, grid, dim3(64), 0, st, g);
+    else hipLaunchKernelGGL(bpe_general_kernel<false>, grid, dim3(64), 0, st, g);
+  };
   int slot = -1;
   bool timed_fast = false;
   if (m->timing) {
@@ -1417,9 +1435,10 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
     }
     BPE_TRY(ws->w_scratch.Reserve(threads * slab));
     GenBpeArgs g{a, nullptr, nullptr, n, ws->w_scratch.as<uint8_t>(), slab, max_nb, status + kStError,
-                 m->bpe.has_user_defined ? 1 : 0, nullptr, nullptr, static_cast<uint32_t>(threads)};
+                 m->bpe.has_user_defined ? 1 : 0, nullptr, nullptr, static_cast<uint32_t>(threads),
+                 drop.threshold, drop.seed, drop.index_base};
     if (slot >= 0) BPE_TRY(hipEventRecord(ws->ev[0], st));
-    if (n) hipLaunchKernelGGL(bpe_general_kernel, dim3((threads + 63) / 64), dim3(64), 0, st, g);
+    if (n) general(dim3((threads + 63) / 64), g);
     BPE_TRY(hipGetLastError());
     if (slot >= 0) BPE_TRY(hipEventRecord(ws->ev[1], st));
   } else if (n) {
@@ -1427,7 +1446,43 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
     // per wave from the device-side list.
     BPE_TRY(ws->w_rest.Reserve(nn * 4));
     if (slot >= 0) BPE_TRY(hipEventRecord(ws->tev[2 * slot], st));
-    if (m->bpe.lane_ok) {
+    if (c.drop) {
+      // One sentence per wave with the probed pairs masked; the short-slab
+      // pass first unless SPM_HIP_BPE_DROPOUT_SHORT=0 (A/B knob).
+      static const int kShortKnob = [] {
+        const char *e = std::getenv("SPM_HIP_BPE_DROPOUT_SHORT");
+        return e ? std::atoi(e) : 1;
+      }();
+      BpeDropoutLaunch d{};
+      d.t.units = a.units;
+      d.t.values = a.values;
+      d.t.entry_piece = a.entry_piece;
+      d.t.entry_out = a.entry_out;
+      d.t.piece_out = a.piece_out;
+      d.t.pair_ent = a.pair_ent;
+      d.t.pair_mask = a.pair_mask;
+      d.t.root_base = a.root_base;
+      d.t.unk_id = a.unk_id;
+      d.t.irregular = a.irregular;
+      d.t.bytes = a.bytes;
+      d.t.slot_ids = a.slot_ids;
+      d.t.slot_len = a.slot_len;
+      d.off = a.off;
+      d.n = n;
+      d.ntok = a.ntok;
+      d.flagged = a.flagged;
+      d.status = status;
+      d.capacity = cap;
+      d.chain = c.out_status;
+      d.threshold = drop.threshold;
+      d.seed = drop.seed;
+      d.index_base = drop.index_base;
+      d.rest = kShortKnob ? ws->w_rest.as<uint32_t>() : nullptr;
+      d.rest_count = kShortKnob ? status + 8 : nullptr;
+      BPE_TRY(LaunchBpeDropout(d, st));
+    } else if (kFastOnly) {
+      // (nothing first: bpe_fast_kernel below takes every sentence)
+    } else if (m->bpe.lane_ok) {
       BPE_TRY(ws->w_slot_ids.Reserve(cap * 4));
       if (c.len) BPE_TRY(ws->w_slot_len.Reserve(cap * 4));
       a.lane_ids = ws->w_slot_ids.as<int32_t>();
@@ -1448,10 +1503,12 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
       hipLaunchKernelGGL(bpe_half_kernel, dim3(hblocks), dim3(256), 0, st, a, ws->w_rest.as<uint32_t>(), status + 8);
     }
     BPE_TRY(hipGetLastError());
-    const uint64_t blocks64 = (n * 64 + 255) / 256;
-    hipLaunchKernelGGL(bpe_fast_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>(blocks64, 8192u))), dim3(256),
-                       0, st, a, ws->w_rest.as<uint32_t>(), status + 8);
-    BPE_TRY(hipGetLastError());
+    if (!c.drop) {
+      const uint64_t blocks64 = (n * 64 + 255) / 256;
+      hipLaunchKernelGGL(bpe_fast_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>(blocks64, 8192u))), dim3(256),
+                         0, st, a, kFastOnly ? nullptr : ws->w_rest.as<uint32_t>(), status + 8);
+      BPE_TRY(hipGetLastError());
+    }
     timed_fast = slot >= 0;  // the timed span ends after the output compaction below
     const GeneralPool gp = PlanGeneralPool(cap, 128, 2048, [](uint32_t nb) { return BpeGeneralSlabBytes(nb); });
     BPE_TRY(ws->w_scratch.Reserve(gp.pool));
@@ -1461,12 +1518,13 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
     const int32_t ud = m->bpe.has_user_defined ? 1 : 0;
     if (slot >= 0) BPE_TRY(hipEventRecord(ws->ev[0], st));
     GenBpeArgs g1{a, ws->w_flagged.as<uint32_t>(), status + kStFlagged, 0, ws->w_scratch.as<uint8_t>(), gp.slab,
-                  gp.small_nb, status + kStError, ud, ovf, status + kStOverflow, gp.lanes};
-    hipLaunchKernelGGL(bpe_general_kernel, dim3((gp.lanes + 63) / 64), dim3(64), 0, st, g1);
+                  gp.small_nb, status + kStError, ud, ovf, status + kStOverflow, gp.lanes,
+                  drop.threshold, drop.seed, drop.index_base};
+    general(dim3((gp.lanes + 63) / 64), g1);
     BPE_TRY(hipGetLastError());
     GenBpeArgs g2{a, ovf, status + kStOverflow, 0, ws->w_scratch.as<uint8_t>(), gp.pool, gp.big_nb,
-                  status + kStError, ud, nullptr, nullptr, 1};
-    hipLaunchKernelGGL(bpe_general_kernel, dim3(1), dim3(64), 0, st, g2);
+                  status + kStError, ud, nullptr, nullptr, 1, drop.threshold, drop.seed, drop.index_base};
+    general(dim3(1), g2);
     BPE_TRY(hipGetLastError());
     if (slot >= 0) BPE_TRY(hipEventRecord(ws->ev[1], st));
   }

@@ -99,6 +99,13 @@ struct EncodeWorkspace {
   void Release();
 };
 
+// BPE-dropout of one call (bpe_dropout.hip): the pair named (start, end) of
+// sentence i is dropped when the 53 bits of SampleDraw(SampleKey(seed,
+// index_base + i), start << 32 | end) are below threshold = ceil(alpha * 2^53).
+struct BpeDropout {
+  uint64_t threshold, seed, index_base;
+};
+
 // One encode call (device pointers, all enqueued on st).  capacity: the
 // caller's bound on offsets[n] (every workspace buffer is sized from it).
 struct EncodeCall {
@@ -113,6 +120,7 @@ struct EncodeCall {
   hipStream_t st;
   bool host_sized;       // general kernel over every sentence, scratch sized on the host
   uint32_t max_nb;       // host_sized: longest sentence
+  const BpeDropout *drop = nullptr;  // BPE models: SampleEncode (BPE-dropout) instead of Encode
 };
 
 // Scratch plan of the device-count general path: `lanes` slabs for sentences

@@ -510,6 +510,33 @@ struct BpeRawArgs {
 hipError_t LaunchBpeSmall(const BpeLineArgs &a, const CoopCall &c, hipStream_t st);
 hipError_t LaunchBpeRaw(const BpeRawArgs &s, const CoopCall &c, hipStream_t st);
 
+// BPE-dropout batch tier (bpe_dropout.hip): one normalized sentence per
+// wavefront, BpeEncodeLineWave with each probed pair masked by the sentence's
+// draw stream (sample_rng.h: key SampleKey(seed, index_base + i), draw number
+// start << 32 | end of the pair's bytes, dropped when the draw's 53 bits are
+// below `threshold` = ceil(alpha * 2^53)).  t: the model's tables with bytes =
+// the batch, slot_ids / slot_len (nullable) the right-aligned slots; stage_*
+// unused.  A sentence it does not take (over kBpeLineMaxBytes bytes, a pushed
+// UNUSED piece, a char outside an irregular vocabulary) is flagged for the
+// general kernel (ntok = ~0, `flagged`, status[kStFlagged / kStMaxNb]).
+// rest / rest_count (nullable, zeroed count): with them the sentences of <=
+// kBpeDropShortBytes bytes run first on slabs of that size (more waves per
+// CU) and the longer ones from the `rest` list on full slabs.
+constexpr uint32_t kBpeDropShortBytes = 128;
+struct BpeDropoutLaunch {
+  BpeLineArgs t;
+  const uint64_t *off;
+  uint64_t n;
+  uint32_t *ntok;
+  uint32_t *flagged;
+  uint32_t *status;          // kStWords
+  uint64_t capacity;         // caller's bound on off[n]
+  const uint32_t *chain;     // asynchronous chain status (nullable)
+  uint64_t threshold, seed, index_base;
+  uint32_t *rest, *rest_count;
+};
+hipError_t LaunchBpeDropout(const BpeDropoutLaunch &d, hipStream_t st);
+
 // Resident service kernel for small calls (coop_service_kernel): one block
 // polls `box` in pinned coherent host memory; the host writes `call` and
 // then `seq` = (sequence & 0x3FFFFFFF) | kind << 30 (kind 1 = normalized

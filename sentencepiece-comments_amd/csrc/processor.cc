@@ -340,7 +340,10 @@ Status SentencePieceProcessor::SampleEncodeBatch(const std::vector<std::string> 
   if (!status_.ok()) return status_;
   if (nbest_size > 512) return Err(SPM_INTERNAL, "nbest_size must be nbest_size <= 512");
   if (nbest_size == 0 || nbest_size == 1) return RunBatch(inputs, ids, pieces, nullptr);
-  if (nbest_size > 1)
+  // A BPE model samples by BPE-dropout with probability alpha, whatever
+  // nbest_size is (the package ignores it there).
+  const bool bpe = proto_.trainer_spec.model_type == kBpe;
+  if (nbest_size > 1 && !bpe)
     return Err(SPM_UNIMPLEMENTED,
                "SampleEncode among the n best (nbest_size > 1) is not implemented on the device; "
                "use nbest_size=-1 to sample from the whole lattice");
@@ -526,9 +529,13 @@ Status SentencePieceProcessor::DeviceEncode(const std::vector<std::string> &inpu
   int32_t *d_ids = static_cast<int32_t *>(dev_.Get(kIds, std::max<uint64_t>(total, 1) * 4));
   uint32_t *d_len = static_cast<uint32_t *>(dev_.Get(kLen, std::max<uint64_t>(total, 1) * 4));
   if (!d_tok || !d_ids || !d_len) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
-  st = FromC(sample ? spm_hip_sample_encode_batch(model_, d_norm, d_norm_off, n, sample->theta, sample->seed,
-                                                  sample->index_base, d_ids, d_len, d_tok, nullptr)
-                    : spm_hip_encode_batch(model_, d_norm, d_norm_off, n, d_ids, d_len, d_tok, nullptr));
+  if (sample && proto_.trainer_spec.model_type == kBpe)  // BPE-dropout: theta is the drop probability
+    st = FromC(spm_hip_bpe_dropout_encode_batch(model_, d_norm, d_norm_off, n, sample->theta, sample->seed,
+                                                sample->index_base, d_ids, d_len, d_tok, nullptr));
+  else
+    st = FromC(sample ? spm_hip_sample_encode_batch(model_, d_norm, d_norm_off, n, sample->theta, sample->seed,
+                                                    sample->index_base, d_ids, d_len, d_tok, nullptr)
+                      : spm_hip_encode_batch(model_, d_norm, d_norm_off, n, d_ids, d_len, d_tok, nullptr));
   if (!st.ok()) return st;
   *b = DeviceBatch{d_norm, d_norm_off, d_ids, d_len, d_tok, total};
   return Status::Ok();

@@ -61,10 +61,14 @@ class SentencePieceProcessor {
   // SampleEncode (sentencepiece_processor.cc:622-659), batched.  nbest_size
   // > 512 is an error; 0 or 1 is exactly Encode; < 0 draws one segmentation
   // per line from the unigram lattice on the device with inverse temperature
-  // alpha (spm_hip_sample_encode_batch; a model that is not unigram gives
+  // alpha (spm_hip_sample_encode_batch; a WORD or CHAR model gives
   // SPM_UNIMPLEMENTED); > 1 (sampling among the n best) is SPM_UNIMPLEMENTED:
   // use nbest_size = -1 (NBestEncode below returns the n best themselves).
-  // Unknown-run merge and the
+  // A BPE model samples by BPE-dropout for every nbest_size but 0 and 1 (the
+  // package ignores nbest_size there; 0 and 1 staying Encode is this
+  // processor's contract): the merge loop of Encode with each candidate merge
+  // skipped with probability alpha (spm_hip_bpe_dropout_encode_batch).
+  // Unknown-run merge (or the byte-fallback expansion) and the
   // extra options apply as in Encode.  Line i of the k-th sampled call uses
   // the random stream of global index (lines sampled so far) + i under the
   // processor's seed, so repeated calls on one line give fresh draws and a
@@ -178,6 +182,8 @@ class SentencePieceProcessor {
   // the lines cross near 21 k tokens, and the next power of two is used.
   static constexpr uint64_t kDecodeDeviceMinTokens = 32768;
 
+  // The model is a BPE model (its SampleEncode is BPE-dropout).
+  bool IsBpe() const { return proto_.trainer_spec.model_type == kBpe; }
   int GetPieceSize() const;
   int PieceToId(const std::string &piece) const;
   const std::string &IdToPiece(int id) const;

@@ -4,7 +4,9 @@
 // --alpha) (spm_encode_main.cc:133-144): --nbest_size=-1 samples from the
 // whole lattice on the device, 0 or 1 is the plain encode; the reference's
 // default of 10 (sampling among the n best) is not implemented and exits
-// with a message.  nbest_* is NBestEncode(line, --nbest_size)
+// with a message.  With a BPE model sample_* is BPE-dropout with probability
+// --alpha, whatever --nbest_size is (the package ignores it there).
+// nbest_* is NBestEncode(line, --nbest_size)
 // (spm_encode_main.cc:154-169): one output line per path of every input
 // line, best first.  --random_seed (not in the reference) makes a run
 // reproducible.
@@ -58,7 +60,8 @@ void Usage(const char *argv0) {
             << "   --extra_options (':' separated encoder extra options, e.g., "
                "\"reverse:bos:eos\")  type: string default: \n"
             << "   --nbest_size (nbest_*: number of segmentations per line; sample_*: -1 samples from the "
-               "whole lattice, 0 or 1 is the best segmentation, larger values are not implemented)  "
+               "whole lattice, 0 or 1 is the best segmentation, larger values are not implemented; ignored with a "
+               "BPE model, which samples by BPE-dropout)  "
                "type: int32 default: 10\n"
             << "   --alpha (smoothing parameter for sampling mode)  type: double default: 0.5\n"
             << "   --vocabulary (Restrict the vocabulary. The encoder only emits the tokens in \"vocabulary\" "
@@ -220,7 +223,7 @@ int main(int argc, char **argv) {
       batch.clear();
       return;
     }
-    auto s = sample ? sp.SampleEncodeBatch(batch, f.nbest_size, f.alpha, want_ids ? &ids : nullptr,
+    auto s = sample ? sp.SampleEncodeBatch(batch, sp.IsBpe() ? -1 : f.nbest_size, f.alpha, want_ids ? &ids : nullptr,
                                            want_ids ? nullptr : &pieces)
                     : sp.EncodeBatch(batch, want_ids ? &ids : nullptr, want_ids ? nullptr : &pieces);
     if (!s.ok()) Die(s.message);

@@ -992,12 +992,14 @@ int EncodeEnqueue(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const spm_amd:
 // encode, waits, and reports the status the reference's Encode would return.
 // A flagged sentence too long for the device general pass (kStError) makes
 // it re-run the batch with host-sized scratch.
+// drop (BPE models): SampleEncode with BPE-dropout instead of Encode.
 int EncodeBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t *d_bytes, const uint64_t *d_off,
-                   uint64_t n, int32_t *d_ids, uint32_t *d_len, uint64_t *d_tok, hipStream_t st) {
+                   uint64_t n, int32_t *d_ids, uint32_t *d_len, uint64_t *d_tok, hipStream_t st,
+                   const spm_amd::BpeDropout *drop = nullptr) {
   uint64_t total = 0;
   int rc = BatchBytes(ws, d_off, n, st, &total);
   if (rc != SPM_OK) return rc;
-  spm_amd::EncodeCall c{d_bytes, d_off, n, total, d_ids, d_len, d_tok, nullptr, st, NeedsHostSized(m), 0};
+  spm_amd::EncodeCall c{d_bytes, d_off, n, total, d_ids, d_len, d_tok, nullptr, st, NeedsHostSized(m), 0, drop};
   if (c.host_sized && (rc = LongestSentence(d_off, n, st, &c.max_nb)) != SPM_OK) return rc;
   ws->stats = spm_hip_encode_stats{};
   if ((rc = EncodeEnqueue(m, ws, c)) != SPM_OK) return rc;
@@ -3096,6 +3098,74 @@ int spm_hip_sample_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, con
   rc = SampleBlocking(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), n, theta, seed, index_base,
                       ws->h_ids.as<int32_t>(), len ? ws->h_len.as<uint32_t>() : nullptr, ws->h_tok.as<uint64_t>(),
                       st);
+  if (rc != SPM_OK) return rc;
+  return FetchHostBatch(m, ws.get(), n, ids, len, tok, st);
+}
+
+// ---------------------------------------------------------------------------
+// BPE-dropout (bpe_dropout.hip, bpe_general_kernel<true>): EncodeBlocking's
+// tiers with every popped pair masked by the sentence's draw stream.
+namespace {
+
+// ceil(alpha * 2^53) clamped to [0, 2^53]: a draw's 53 bits are below it
+// exactly when SampleDraw < (double) alpha (alpha * 2^53 is exact in double).
+bool BpeDropoutThreshold(float alpha, uint64_t *t) {
+  if (std::isnan(alpha)) return false;
+  const double a = static_cast<double>(alpha);
+  *t = a <= 0.0 ? 0ull : a >= 1.0 ? (1ull << 53) : static_cast<uint64_t>(std::ceil(a * 0x1.0p53));
+  return true;
+}
+
+int BpeDropoutArgsCheck(const spm_hip_model *m, float alpha, spm_amd::BpeDropout *drop) {
+  if (!BpeDropoutThreshold(alpha, &drop->threshold)) return Fail(SPM_INVALID_ARGUMENT, "alpha must not be NaN");
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  if (m->model_type != spm_amd::kBpe)
+    return Fail(SPM_UNIMPLEMENTED, "BPE-dropout is implemented for BPE models only");
+  return SPM_OK;
+}
+
+}  // namespace
+
+int spm_hip_bpe_dropout_threshold(float alpha, uint64_t *threshold) {
+  if (!threshold) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (!BpeDropoutThreshold(alpha, threshold)) return Fail(SPM_INVALID_ARGUMENT, "alpha must not be NaN");
+  return SPM_OK;
+}
+
+int spm_hip_bpe_dropout_encode_batch(spm_hip_model *m, const uint8_t *d_bytes, const uint64_t *d_off, uint64_t n,
+                                     float alpha, uint64_t seed, uint64_t index_base, int32_t *d_ids,
+                                     uint32_t *d_len, uint64_t *d_tok, void *stream) {
+  spm_amd::TraceRange trace_range_("spm_hip_bpe_dropout_encode_batch");
+  if (!m || (!d_off) || (!d_tok) || (n && !d_ids)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  spm_amd::BpeDropout drop{0, seed, index_base};
+  const int rc = BpeDropoutArgsCheck(m, alpha, &drop);
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForStream(m, st));
+  return EncodeBlocking(m, ws.get(), d_bytes, d_off, n, d_ids, d_len, d_tok, st, &drop);
+}
+
+int spm_hip_bpe_dropout_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                                          float alpha, uint64_t seed, uint64_t index_base, int32_t *ids,
+                                          uint32_t *len, uint64_t *tok) {
+  spm_amd::TraceRange trace_range_("spm_hip_bpe_dropout_encode_batch_host");
+  if (!m || !off || !tok) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  spm_amd::BpeDropout drop{0, seed, index_base};
+  int rc = BpeDropoutArgsCheck(m, alpha, &drop);
+  if (rc != SPM_OK) return rc;
+  if (n >= 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  if ((rc = HostOffsetsCheck(off, n)) != SPM_OK) return rc;
+  const uint64_t total = off[n];
+  if (total && (!bytes || !ids)) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  spm_amd::WorkspaceLease ws;
+  SPM_LEASE(ws, ws.ForHost(m));
+  hipStream_t st = ws.stream();
+  rc = StageHostBatch(ws.get(), bytes, off, n, total, len != nullptr, st);
+  if (rc != SPM_OK) return rc;
+  rc = EncodeBlocking(m, ws.get(), ws->h_in.as<uint8_t>(), ws->h_off.as<uint64_t>(), n, ws->h_ids.as<int32_t>(),
+                      len ? ws->h_len.as<uint32_t>() : nullptr, ws->h_tok.as<uint64_t>(), st, &drop);
   if (rc != SPM_OK) return rc;
   return FetchHostBatch(m, ws.get(), n, ids, len, tok, st);
 }

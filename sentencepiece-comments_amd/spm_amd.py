@@ -49,6 +49,7 @@ EXPORTED = [
     "spm_hip_estep_kernel_times", "spm_hip_device_bytes", "spm_hip_device_peak_reset",
     "spm_hip_encode_raw_small_host", "spm_hip_model_piece_lookup",
     "spm_hip_sample_encode_batch", "spm_hip_sample_encode_batch_host", "spm_hip_sample_uniform",
+    "spm_hip_bpe_dropout_encode_batch", "spm_hip_bpe_dropout_encode_batch_host", "spm_hip_bpe_dropout_threshold",
     "spm_hip_entropy_batch", "spm_hip_entropy_batch_host", "spm_hip_sample_encode_and_score_batch",
     "spm_hip_sample_encode_and_score_batch_host", "spm_hip_sample_seed",
     "spm_hip_nbest_encode_batch", "spm_hip_nbest_encode_batch_host", "spm_hip_model_set_nbest_max_hyps",
@@ -216,6 +217,9 @@ def lib():
         L.spm_hip_sample_encode_batch.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P, P]
         L.spm_hip_sample_encode_batch_host.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P]
         L.spm_hip_sample_uniform.argtypes = [U64, U64, U64, ctypes.POINTER(ctypes.c_double)]
+        L.spm_hip_bpe_dropout_encode_batch.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P, P]
+        L.spm_hip_bpe_dropout_encode_batch_host.argtypes = [P, P, P, U64, ctypes.c_float, U64, U64, P, P, P]
+        L.spm_hip_bpe_dropout_threshold.argtypes = [ctypes.c_float, ctypes.POINTER(U64)]
         L.spm_hip_entropy_batch.argtypes = [P, P, P, U64, ctypes.c_float, P, P, P]
         L.spm_hip_entropy_batch_host.argtypes = [P, P, P, U64, ctypes.c_float, P, P]
         L.spm_hip_sample_encode_and_score_batch.argtypes = [P, P, P, U64, ctypes.c_uint32, ctypes.c_float, U64, U64,
@@ -276,6 +280,14 @@ def sample_uniform(seed, index, draw):
     m = (1 << 64) - 1
     _check(lib().spm_hip_sample_uniform(seed & m, index & m, draw & m, ctypes.byref(u)))
     return u.value
+
+
+def bpe_dropout_threshold(alpha):
+    """ceil(alpha * 2^53) clamped to [0, 2^53]: the BPE-dropout kernels drop a
+    pair when its draw's 53 bits are below it (spm_hip_bpe_dropout_threshold)."""
+    t = ctypes.c_uint64()
+    _check(lib().spm_hip_bpe_dropout_threshold(alpha, ctypes.byref(t)))
+    return t.value
 
 
 def sample_seed(seed, sample):
@@ -587,6 +599,32 @@ class DeviceModel:
                                                    ctypes.c_void_p(d_len) if d_len else None,
                                                    ctypes.c_void_p(d_tok),
                                                    ctypes.c_void_p(stream) if stream else None))
+
+    def bpe_dropout_encode_csr_host(self, buf, off, alpha, seed, index_base=0, with_lens=False):
+        """SampleEncode of a BPE model (BPE-dropout) on host CSR sentences: the
+        merge loop of Encode with every candidate merge skipped with
+        probability alpha; sentence i uses the random stream of global index
+        index_base + i under seed.  Returns what encode_csr_host returns."""
+        n = len(off) - 1
+        cap = max(int(off[-1]), 1)
+        ids = np.zeros(cap, dtype=np.int32)
+        lens = np.zeros(cap, dtype=np.uint32) if with_lens else None
+        to = np.zeros(n + 1, dtype=np.uint64)
+        _check(self._L.spm_hip_bpe_dropout_encode_batch_host(self.h, _p(buf), _p(off), n, alpha, seed, index_base,
+                                                             _p(ids), _p(lens) if with_lens else None, _p(to)))
+        k = int(to[-1])
+        if with_lens:
+            return ids[:k], lens[:k], to
+        return ids[:k], to
+
+    def bpe_dropout_encode_device(self, d_bytes, d_off, n, alpha, seed, d_ids, d_tok, index_base=0, d_len=None,
+                                  stream=None):
+        """spm_hip_bpe_dropout_encode_batch on device pointers (ints); blocking."""
+        _check(self._L.spm_hip_bpe_dropout_encode_batch(self.h, ctypes.c_void_p(d_bytes), ctypes.c_void_p(d_off), n,
+                                                        alpha, seed, index_base, ctypes.c_void_p(d_ids),
+                                                        ctypes.c_void_p(d_len) if d_len else None,
+                                                        ctypes.c_void_p(d_tok),
+                                                        ctypes.c_void_p(stream) if stream else None))
 
     def entropy_csr_host(self, buf, off, theta, with_log_z=False):
         """CalculateEntropy of host CSR sentences at inverse temperature theta:
