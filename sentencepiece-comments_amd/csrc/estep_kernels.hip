@@ -122,42 +122,6 @@ namespace {
 constexpr int kEBlock = 256;
 constexpr uint32_t kRTRows = 32;  // tile-transposed records kept per lane (EArgs::RT)
 
-// A/B knobs of the E-step launch (read once per process).
-struct EStepKnobs {
-  // SPM_HIP_ESTEP_PAIR=1: two positions per lane in flight (slower: the
-  // kernel is VALU-heavy, and the pair costs 3 waves and spills).
-  bool pair = false;
-  // SPM_HIP_ESTEP_ROLL=0: per-depth node emission instead of the rolled
-  // per-lane loop (c4 FAST 0.274 -> 0.249, PARITY 0.290 -> 0.266 s/epoch
-  // with the rolled one, profiles/r04h_estep_roll_ab.txt).
-  bool roll = true;
-  // SPM_HIP_ESTEP_STAGE=1: deferred PARITY records staged in LDS and written
-  // as one run per lane and flush (PMC writes of the backward kernel 3.48 ->
-  // 1.29 GB per launch at the 12.5 M-sentence epoch, but 23 spilled VGPRs
-  // instead of 14 and PARITY 0.2628 -> 0.264-0.267 s/epoch, gpurun_out/r05c).
-  bool stage = false;
-  // SPM_HIP_ESTEP_AT=0 / SPM_HIP_ESTEP_RT=0: alpha / deferred records in
-  // their range layout instead of tile-transposed (EArgs::AT / RT).
-  bool transposed_alpha = true;
-  bool transposed_records = true;
-};
-
-const EStepKnobs &Knobs() {
-  static const EStepKnobs k = [] {
-    auto flag = [](const char *name, bool dflt) {
-      const char *e = std::getenv(name);
-      return e ? std::atoi(e) != 0 : dflt;
-    };
-    EStepKnobs x;
-    x.pair = flag("SPM_HIP_ESTEP_PAIR", false);
-    x.roll = flag("SPM_HIP_ESTEP_ROLL", true);
-    x.stage = flag("SPM_HIP_ESTEP_STAGE", false);
-    x.transposed_alpha = flag("SPM_HIP_ESTEP_AT", true);
-    x.transposed_records = flag("SPM_HIP_ESTEP_RT", true);
-    return x;
-  }();
-  return k;
-}
 // Accumulate calls of at least this many sentences use the byte kernel's
 // E-step mode (its TrainerModel build costs ~0.1 s per piece list).
 constexpr uint64_t kByteForwardMinSentences = 1ull << 20;
@@ -221,11 +185,8 @@ struct EArgs {
   // and per sentence the records kept (written at the end of its range).
   const uint8_t *__restrict__ drop_exp;
   uint32_t *__restrict__ kept;
-  // PARITY records stored with nontemporal hints (SPM_HIP_ESTEP_NT): they are
-  // read back only by later kernels, so they need not displace the trie's
-  // lines in L2.
-  int nt;
-  // Deferred record values (set while the record drop is active): a record
+  // Deferred record values (set exactly while the record drop is active,
+  // i.e. with drop_exp): a record
   // holds the float exponent ex of c = freq * exp(ex) instead of c (in the
   // vals buffer's storage), estep_compact_records_kernel computes c for the
   // kept ones only, and the drop test decides most records from ex alone.
@@ -246,24 +207,14 @@ struct EArgs {
 
 // One PARITY record (key, fp64 contribution) at slot w.
 __device__ __forceinline__ void StoreRecord(const EArgs &a, uint64_t w, uint32_t key, double c) {
-  if (a.nt) {
-    __builtin_nontemporal_store(key, a.keys + w);
-    __builtin_nontemporal_store(c, a.vals + w);
-  } else {
-    a.keys[w] = key;
-    a.vals[w] = c;
-  }
+  a.keys[w] = key;
+  a.vals[w] = c;
 }
 
 // A deferred record (key, ex) at slot w.
 __device__ __forceinline__ void StoreRecordEx(const EArgs &a, uint64_t w, uint32_t key, float ex) {
-  if (a.nt) {
-    __builtin_nontemporal_store(key, a.keys + w);
-    __builtin_nontemporal_store(ex, a.exs + w);
-  } else {
-    a.keys[w] = key;
-    a.exs[w] = ex;
-  }
+  a.keys[w] = key;
+  a.exs[w] = ex;
 }
 
 // The PARITY record of one node, written at --w unless dropped: its value is
@@ -297,10 +248,8 @@ __device__ __forceinline__ void ParityRecord(const EArgs &a, uint64_t &w, uint32
     StoreRecordEx(a, w, key, ex);
     return;
   }
+  // No drop (texp = 0 throughout): the record holds its value.
   const double c = static_cast<double>(freq_f) * exp(static_cast<double>(ex));
-  // c >= 0 here (the drop is off once a negative freq is seen); NaN and
-  // negative values never pass the test.
-  if (texp && static_cast<uint64_t>(__double_as_longlong(c)) >> 52 < texp + 871u) return;
   --w;
   StoreRecord(a, w, key, c);
 }
@@ -653,44 +602,44 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(WPE))) 
   }
 }
 
-// kVar bit 0: lagged emits — node d's id/score loads are issued right after
-// walk step d and the node is emitted at step d + 1 (its loads have landed by
-// then), so the 2 x 16 id/score registers of the batched version are not live
-// across the walk.  PARITY records of a position are then written from the
-// block's end backwards: a position's trie nodes have distinct piece ids, so
-// their relative order does not matter to the per-key fold; the UNK record
-// (id 0, which can equal a multi-char trie piece's id 0) gets the block's last
-// slot, reserved once step 1 has decided it, so it still follows every trie
-// node as in begin_nodes order.  Bit 1: PARITY-only build without the FAST
-// LDS accumulators (47 -> 15 KB of LDS per block).
+// kVar bits of estep_backward_kernel (the launch sites name them; variants
+// that lost their A/B are in tools/estep_variants/README.md).
+constexpr int kBwdParityOnly = 2;  // PARITY-only build: no FAST LDS accumulators, record drop
+constexpr int kBwdRoll = 8;        // rolled node emission (W = 16)
+constexpr int kBwdAT = 32;         // tile-transposed alpha / lane map / records of the byte-kernel forward
+
+// The backward pass: per sentence (one per lane) and char position q, from
+// the last one down, the walk collects begin_nodes[q]'s trie nodes (id and
+// score per ring depth d = length in chars), then the nodes are emitted: each
+// one's record (PARITY) or accumulation (FAST), and Bt[q] as the LogSumExp
+// over them in begin_nodes order (trie nodes by ascending length, then UNK).
+// Two emissions exist:
+//  - per depth (W = 32): one predicated emission per ring depth (a wave pays
+//    every depth any lane has a node at: the union).  A position's records
+//    take the next g slots below the cursor and are written upwards, in
+//    begin_nodes order.
+//  - rolled (kBwdRoll, W = 16): a loop over the lane's own present nodes (a
+//    wave runs it max-over-lanes times); the loop body selects the node's
+//    registers.  Records are written from the sentence range's end
+//    downwards, one slot at a time, so a dropped record takes no slot.  A
+//    position's trie nodes have distinct piece ids, so their relative order
+//    does not matter to the per-key fold; but UNK's record has id 0, which
+//    can equal a trie piece's id 0 (also the TrainerModel's UNK id), and in
+//    begin_nodes order it follows every trie node.  Records go downwards, so
+//    UNK's is written first: it then sits above the trie nodes' ones.  (UNK
+//    records carry no bound and are always kept.)
+// kBwdParityOnly drops the FAST LDS accumulators (47 -> 15 KB of LDS per
+// block) and adds the record drop.  kBwdAT (with kBwdRoll): the byte-kernel
+// forward pass's tile-transposed alpha and lane assignment (EArgs::AT,
+// lanemap), and with kBwdParityOnly the tile-transposed deferred records
+// (EArgs::RT).
 template <int W, int WPE, int kVar = 0>
 __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(WPE))) void estep_backward_kernel(EArgs a) {
-  constexpr bool kLag = (kVar & 1) != 0;
-  constexpr bool kParityOnly = (kVar & 2) != 0;
-  // kPair: two char positions per lane in flight (kLag is ignored): the
-  // walks of position q and of the char start before it issue their trie
-  // gathers together, then both positions' nodes are emitted in descending
-  // position order (the emission needs q's Bt before the earlier one's).
-  constexpr bool kPair = (kVar & 4) != 0;
-  // kRoll: a position's nodes are emitted by a loop over the lane's own
-  // present nodes (a wave runs it max-over-lanes times) instead of one
-  // predicated emission per ring depth (a wave pays every depth any lane has
-  // a node at: the union).  The loop body selects the node's registers.
-  constexpr bool kRoll = (kVar & 8) != 0;
-  // kStage (with kRoll and kParityOnly, deferred records): a lane's kept
-  // records go to an LDS ring of kRecStage entries and are written to their
-  // slots as one contiguous run per flush.  Written one by one, the 4-byte
-  // key / ex stores of 64 lanes hit 64 scattered lines per instruction: L2
-  // evicted half-written lines (write traffic) and filled them for the
-  // partial writes (read traffic), and the walk's trie lines went with them.
-  constexpr bool kStage = (kVar & 16) != 0 && kRoll && kParityOnly;
-  // kAT (with kRoll): the byte-kernel forward pass's tile-transposed alpha
-  // and lane assignment (EArgs::AT, lanemap), and with kParityOnly the
-  // tile-transposed deferred records (EArgs::RT).
-  constexpr bool kAT = (kVar & 32) != 0 && kRoll;
-  constexpr uint32_t kRecStage = 8;
-  __shared__ uint32_t lds_rk[kStage ? kRecStage * kEBlock : 1];
-  __shared__ float lds_rx[kStage ? kRecStage * kEBlock : 1];
+  static_assert((kVar & ~(kBwdParityOnly | kBwdRoll | kBwdAT)) == 0, "unknown kVar bit");
+  static_assert(!(kVar & kBwdAT) || (kVar & kBwdRoll), "kBwdAT needs kBwdRoll");
+  constexpr bool kParityOnly = (kVar & kBwdParityOnly) != 0;
+  constexpr bool kRoll = (kVar & kBwdRoll) != 0;
+  constexpr bool kAT = (kVar & kBwdAT) != 0;
   // FAST: the expected counts of the kHot highest-score (= most frequent)
   // pieces are privatised per block in LDS and flushed once, so the hot ids
   // ("▁", single letters) do not serialise on global fp64 atomics.
@@ -774,149 +723,9 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(WPE))) 
     for (int d = 0; d < W; ++d) Br[d] = 0.f;  // Br[1] = Bt[len] = 0 (EOS)
     uint64_t cursor = a.mode == SPM_ESTEP_PARITY ? a.rec_off[i] + a.N[i] : 0;
     uint32_t rt_k = 0;  // RT: records this lane kept so far
-    // kStage: records staged in LDS (entry k of nst belongs at slot
-    // w + nst - 1 - k, w = the lane's cursor); written in ascending order.
-    uint32_t nst = 0;
-    auto stage_flush = [&](uint64_t wc) {
-      if constexpr (kStage) {
-        for (uint32_t k = nst; k-- > 0;) {
-          const uint64_t g = wc + nst - 1 - k;
-          a.keys[g] = lds_rk[k * kEBlock + threadIdx.x];
-          a.exs[g] = lds_rx[k * kEBlock + threadIdx.x];
-        }
-        nst = 0;
-      }
-    };
     // Last char start.
     uint32_t q = nb - 1;
     while (q > 0 && ContinuationByte(sb(q))) --q;
-    if constexpr (kPair) {
-      const bool parity = kParityOnly || a.mode == SPM_ESTEP_PARITY;
-      uint64_t w = cursor;  // PARITY records, written from the range's end down
-      // One node's record or FAST accumulation (c = freq * exp(...),
-      // :318-325); PARITY-only drop test as in the lagged kernel.
-      auto record = [&](float A_q, int32_t packed, float sc, float be) {
-        const float ex = __fsub_rn(__fadd_rn(__fadd_rn(A_q, sc), be), Z);
-        const uint32_t id = kParityOnly ? static_cast<uint32_t>(packed) & 0xFFFFFFu : static_cast<uint32_t>(packed);
-        if (parity) {
-          ParityRecord(a, w, bucket * a.V + id, ex, freq_f, lfreq, kParityOnly ? static_cast<uint32_t>(packed) >> 24 : 0u);
-        } else if constexpr (!kParityOnly) {
-          const double c = static_cast<double>(freq_f) * exp(static_cast<double>(ex));
-          const int32_t hs = a.hot_slot[id];
-          if (hs >= 0) atomicAdd(&lds_acc[hs], c);
-          else atomicAdd(&a.acc[id], c);
-        }
-      };
-      // Position q's begin_nodes: records (UNK first: it must sit above the
-      // trie nodes' records, piece 0 may be among them), LogSumExp terms in
-      // the reference order (trie nodes by length, then UNK), Bt[q] into the
-      // ring.  Records of one position have distinct keys but UNK's, so
-      // their order inside the position is free.
-      auto emit_pos = [&](float A_q, const float (&sd)[W], const int32_t (&id)[W], uint64_t pres, bool single) {
-        const bool unk = !single;
-        if (unk) record(A_q, 0, a.unk_score, Br[1]);
-        float bt = 0.f;
-        bool first = true;
-        StaticFor<1, W>([&](auto dc) {
-          constexpr int d = decltype(dc)::value;
-          if ((pres >> d) & 1) {
-            record(A_q, id[d], sd[d], Br[d]);
-            bt = LogSumExpDev(bt, __fadd_rn(sd[d], Br[d]), first);
-            first = false;
-          }
-        });
-        if (unk) bt = LogSumExpDev(bt, __fadd_rn(a.unk_score, Br[1]), first);
-#pragma unroll
-        for (int d = W - 1; d >= 2; --d) Br[d] = Br[d - 1];
-        Br[1] = bt;
-      };
-      const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
-      uint32_t qa = q;
-      for (;;) {
-        const bool hb = qa > 0;
-        uint32_t qb = 0;
-        if (hb) {
-          qb = qa - 1;
-          while (qb > 0 && ContinuationByte(sb(qb))) --qb;
-        }
-        const float A_a = alpha(qa);
-        const float A_b = hb ? alpha(qb) : 0.f;
-        uint32_t ba = a.root_base, bb = a.root_base, pa = qa, pb = qb;
-        bool la = true, lb = hb, one_a = false, one_b = false;
-        float sda[W], sdb[W];
-        int32_t ida[W], idb[W];
-        uint64_t pra = 0, prb = 0;
-        // A chain's char step after its first gather landed: the char's
-        // remaining bytes (multi-byte chars only) and the node, if a leaf.
-        auto finish = [&](auto dc, bool &l, uint32_t &base, uint32_t &p, uint32_t c, uint32_t cl, uint4 x,
-                          float (&sd)[W], int32_t (&id)[W], uint64_t &pres, bool &one) {
-          constexpr int d = decltype(dc)::value;
-          if (!l) return;
-          if ((x.x & 0xFFu) != c || c == 0) {
-            l = false;
-            return;
-          }
-          base = x.x >> 9;
-          for (uint32_t j = 1; j < cl; ++j) {
-            const uint32_t cj = sb(p + j);
-            x = cj ? a.uvis[base ^ cj] : z4;
-            if ((x.x & 0xFFu) != cj || cj == 0) {
-              l = false;
-              return;
-            }
-            base = x.x >> 9;
-          }
-          p += cl;
-          if (x.x & 0x100u) {
-            id[d] = static_cast<int32_t>(x.y);
-            if constexpr (kParityOnly)
-              if (drop && x.w) id[d] |= static_cast<int32_t>(static_cast<uint32_t>(lds_drop[x.w - 1]) << 24);
-            sd[d] = __uint_as_float(x.z);
-            pres |= 1ull << d;
-            if (d == 1) one = true;
-          }
-        };
-        StaticFor<1, W>([&](auto dc) {
-          constexpr int d = decltype(dc)::value;
-          sda[d] = 0.f;
-          sdb[d] = 0.f;
-          ida[d] = 0;
-          idb[d] = 0;
-          // Issue both chains' first-byte gathers, then complete each.
-          uint32_t ca = 0, cb = 0, cla = 0, clb = 0;
-          uint4 xa = z4, xb = z4;
-          if (la) {
-            if (pa >= nb) {
-              la = false;
-            } else {
-              ca = sb(pa);
-              cla = OneCharLenDev(ca);
-              if (cla > nb - pa) cla = nb - pa;
-              xa = d == 1 ? lds_root[ca] : ca ? a.uvis[ba ^ ca] : z4;
-            }
-          }
-          if (lb) {
-            if (pb >= nb) {
-              lb = false;
-            } else {
-              cb = sb(pb);
-              clb = OneCharLenDev(cb);
-              if (clb > nb - pb) clb = nb - pb;
-              xb = d == 1 ? lds_root[cb] : cb ? a.uvis[bb ^ cb] : z4;
-            }
-          }
-          finish(dc, la, ba, pa, ca, cla, xa, sda, ida, pra, one_a);
-          finish(dc, lb, bb, pb, cb, clb, xb, sdb, idb, prb, one_b);
-        });
-        emit_pos(A_a, sda, ida, pra, one_a);
-        if (!hb) break;
-        emit_pos(A_b, sdb, idb, prb, one_b);
-        if (qb == 0) break;
-        qa = qb - 1;
-        while (qa > 0 && ContinuationByte(sb(qa))) --qa;
-      }
-      if (parity) cursor = w;
-    } else
     for (;;) {
       const float A_q = alpha(q);
       uint32_t base_u = a.root_base, p = q;
@@ -959,81 +768,16 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(WPE))) 
           }
         }
       };
-      if constexpr (kLag) {
-        const bool parity = kParityOnly || a.mode == SPM_ESTEP_PARITY;
-        uint64_t w = cursor;  // records written from the sentence range's end down
-        float bt = 0.f;
-        bool first = true, unk = false;
-        // One node's record (c = freq * exp(...), :318-325); kept unless the
-        // drop test proves it cannot change its accumulator.  Packed ids carry
-        // the accumulator bound's biased float exponent in bits 24-31.
-        auto record = [&](int32_t packed, float sc, float be) {
-          const float ex = __fsub_rn(__fadd_rn(__fadd_rn(A_q, sc), be), Z);
-          const uint32_t id = kParityOnly ? static_cast<uint32_t>(packed) & 0xFFFFFFu : static_cast<uint32_t>(packed);
-          if (parity) {
-            // c < 2^(e_exp - 152) = ulp(bound) / 4 is a no-op (ParityRecord).
-            ParityRecord(a, w, bucket * a.V + id, ex, freq_f, lfreq,
-                         kParityOnly ? static_cast<uint32_t>(packed) >> 24 : 0u);
-          } else if constexpr (!kParityOnly) {
-            const double c = static_cast<double>(freq_f) * exp(static_cast<double>(ex));
-            const int32_t hs = a.hot_slot[id];
-            if (hs >= 0) atomicAdd(&lds_acc[hs], c);
-            else atomicAdd(&a.acc[id], c);
-          }
-        };
-        auto lse = [&](float sc, float be) {
-          bt = LogSumExpDev(bt, __fadd_rn(sc, be), first);
-          first = false;
-        };
-        // The UNK node of begin_nodes[q] comes after the trie nodes in the
-        // reference order (its LogSumExp term is applied last), but its record
-        // is written first: records go downwards, so it ends up above the
-        // trie nodes' ones (piece 0, also the TrainerModel's UNK id, may be
-        // among them and its record must precede).
-        // (UNK records carry no bound and are always kept.)
-        StaticFor<1, W + 1>([&](auto dc) {
-          constexpr int d = decltype(dc)::value;
-          if constexpr (d < W) {
-            stepd(dc);
-            if constexpr (d == 1) {
-              unk = !single;
-              if (unk) record(0, a.unk_score, Br[1]);
-            }
-          }
-          if constexpr (d >= 2) {
-            if ((present >> (d - 1)) & 1) {
-              record(idd[d - 1], sd[d - 1], Br[d - 1]);
-              lse(sd[d - 1], Br[d - 1]);
-            }
-          }
-        });
-        if (unk) lse(a.unk_score, Br[1]);
-        if (parity) cursor = w;
-#pragma unroll
-        for (int d = W - 1; d >= 2; --d) Br[d] = Br[d - 1];
-        Br[1] = bt;
-        if (q == 0) break;
-        --q;
-        while (q > 0 && ContinuationByte(sb(q))) --q;
-        continue;
-      }
       StaticFor<1, W>(stepd);
+      const bool unk = !single;
+      float bt = 0.f;
+      bool first = true;
       if constexpr (kRoll) {
         const bool parity = kParityOnly || a.mode == SPM_ESTEP_PARITY;
         uint64_t w = cursor;  // PARITY records, written from the range's end down
         auto rec = [&](int32_t packed, float sc, float be) {
           const float ex = __fsub_rn(__fadd_rn(__fadd_rn(A_q, sc), be), Z);
           const uint32_t id = kParityOnly ? static_cast<uint32_t>(packed) & 0xFFFFFFu : static_cast<uint32_t>(packed);
-          if constexpr (kStage) {
-            if (a.exs) {
-              if (!DeferredKeep(ex, freq_f, lfreq, static_cast<uint32_t>(packed) >> 24)) return;
-              --w;
-              lds_rk[nst * kEBlock + threadIdx.x] = bucket * a.V + id;
-              lds_rx[nst * kEBlock + threadIdx.x] = ex;
-              if (++nst == kRecStage) stage_flush(w);
-              return;
-            }
-          }
           if (parity) {
             if (kAT && kParityOnly && RTt) {  // deferred records, tile-transposed
               if (!DeferredKeep(ex, freq_f, lfreq, static_cast<uint32_t>(packed) >> 24)) return;
@@ -1052,12 +796,9 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(WPE))) 
             else atomicAdd(&a.acc[id], c);
           }
         };
-        // UNK's record first (above the trie nodes' ones, as the lagged
-        // kernel), its LogSumExp term last (begin_nodes order).
-        const bool unk = !single;
+        // UNK's record first (it ends up above the trie nodes' ones, see the
+        // kernel's comment), its LogSumExp term last (begin_nodes order).
         if (unk) rec(0, a.unk_score, Br[1]);
-        float bt = 0.f;
-        bool first = true;
         uint32_t m = static_cast<uint32_t>(present);
         while (m) {
           const uint32_t d = static_cast<uint32_t>(__builtin_ctz(m));  // ascending length
@@ -1078,45 +819,36 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(WPE))) 
         }
         if (unk) bt = LogSumExpDev(bt, __fadd_rn(a.unk_score, Br[1]), first);
         if (parity) cursor = w;
-#pragma unroll
-        for (int d = W - 1; d >= 2; --d) Br[d] = Br[d - 1];
-        Br[1] = bt;
-        if (q == 0) break;
-        --q;
-        while (q > 0 && ContinuationByte(sb(q))) --q;
-        continue;
-      }
-      // begin_nodes[q] order: trie nodes by ascending length, then UNK.
-      const bool unk = !single;
-      const uint32_t g = __popcll(present) + (unk ? 1u : 0u);
-      if (a.mode == SPM_ESTEP_PARITY) cursor -= g;
-      uint64_t w = cursor;
-      float bt = 0.f;
-      bool first = true;
-      auto emit = [&](int32_t id, float sc, float be) {
-        const float ex = __fsub_rn(__fadd_rn(__fadd_rn(A_q, sc), be), Z);
-        if (a.mode == SPM_ESTEP_PARITY) {
-          const uint32_t key = bucket * a.V + static_cast<uint32_t>(id);
-          if (a.exs) StoreRecordEx(a, w, key, ex);
-          else StoreRecord(a, w, key, static_cast<double>(freq_f) * exp(static_cast<double>(ex)));
-          ++w;
-        } else {
-          const double c = static_cast<double>(freq_f) * exp(static_cast<double>(ex));
-          if constexpr (!kParityOnly) {
+      } else {
+        // Per depth, in begin_nodes[q] order.  (a.exs is never set here:
+        // deferred records need the drop, which needs the PARITY-only build.
+        // Without the select the W = 32 build takes 205 VGPRs instead of 198
+        // and other code, which nobody has measured, so it stays.)
+        const uint32_t g = __popcll(present) + (unk ? 1u : 0u);
+        if (a.mode == SPM_ESTEP_PARITY) cursor -= g;
+        uint64_t w = cursor;
+        auto emit = [&](int32_t id, float sc, float be) {
+          const float ex = __fsub_rn(__fadd_rn(__fadd_rn(A_q, sc), be), Z);
+          if (a.mode == SPM_ESTEP_PARITY) {
+            const uint32_t key = bucket * a.V + static_cast<uint32_t>(id);
+            if (a.exs) StoreRecordEx(a, w, key, ex);
+            else StoreRecord(a, w, key, static_cast<double>(freq_f) * exp(static_cast<double>(ex)));
+            ++w;
+          } else if constexpr (!kParityOnly) {
+            const double c = static_cast<double>(freq_f) * exp(static_cast<double>(ex));
             const int32_t hs = a.hot_slot[id];
             if (hs >= 0) atomicAdd(&lds_acc[hs], c);
             else atomicAdd(&a.acc[id], c);
           }
-        }
-        bt = LogSumExpDev(bt, __fadd_rn(sc, be), first);
-        first = false;
-      };
-      auto emitd = [&](auto dc) {
-        constexpr int d = decltype(dc)::value;
-        if ((present >> d) & 1) emit(idd[d], sd[d], Br[d]);
-      };
-      StaticFor<1, W>(emitd);
-      if (unk) emit(0, a.unk_score, Br[1]);
+          bt = LogSumExpDev(bt, __fadd_rn(sc, be), first);
+          first = false;
+        };
+        StaticFor<1, W>([&](auto dc) {
+          constexpr int d = decltype(dc)::value;
+          if ((present >> d) & 1) emit(idd[d], sd[d], Br[d]);
+        });
+        if (unk) emit(0, a.unk_score, Br[1]);
+      }
       // Shift: slot d+1 <- d; slot 1 = Bt[q].
 #pragma unroll
       for (int d = W - 1; d >= 2; --d) Br[d] = Br[d - 1];
@@ -1125,8 +857,6 @@ __global__ __launch_bounds__(kEBlock) __attribute__((amdgpu_waves_per_eu(WPE))) 
       --q;
       while (q > 0 && ContinuationByte(sb(q))) --q;
     }
-    if constexpr (kStage)
-      if (nst) stage_flush(cursor);
     // Records kept: the last `kept` slots of the sentence's range.
     if (kParityOnly && drop) a.kept[i] = static_cast<uint32_t>(a.rec_off[i] + a.N[i] - cursor);
       }();
@@ -2063,6 +1793,41 @@ void ETimingMark(spm_hip_pieces *P, hipStream_t st) {
   }
   P->tev.push_back(e);
 }
+
+// off[0..n] = exclusive scan of the counts (off[n] = their sum) on st; the sum
+// is read back through the pinned slot, so the host waits for the stream.
+int ScanCounts(spm_hip_pieces *P, const uint32_t *counts, uint64_t n, uint64_t *off, uint32_t *pinned_slot,
+               hipStream_t st, uint64_t *total) {
+  size_t tb = 0;
+  hipcub::TransformInputIterator<uint64_t, ToU64E, const uint32_t *> it(counts, ToU64E());
+  E_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, it, off + 1, static_cast<int>(n), st));
+  E_TRY(P->w_tmp.Reserve(tb + 16));
+  E_TRY(hipMemsetAsync(off, 0, 8, st));
+  E_TRY(hipcub::DeviceScan::InclusiveSum(P->w_tmp.ptr, tb, it, off + 1, static_cast<int>(n), st));
+  E_TRY(hipMemcpyAsync(pinned_slot, off + n, 8, hipMemcpyDeviceToHost, st));
+  E_TRY(hipStreamSynchronize(st));
+  std::memcpy(total, pinned_slot, 8);
+  return SPM_OK;
+}
+
+// The backward kernel of a chunk: ring width 32 has one build for both modes
+// (per-depth emission); width 16 is rolled, PARITY in the PARITY-only build
+// (no FAST LDS table, 4 waves/SIMD), each with kBwdAT where the byte-kernel
+// forward pass wrote AT and the lane map.
+void LaunchEStepBackward(int ring_width, unsigned blocks, hipStream_t st, const EArgs &a) {
+  const dim3 g(blocks), b(kEBlock);
+  constexpr int kParityRoll = kBwdParityOnly | kBwdRoll;
+  if (ring_width != 16)
+    hipLaunchKernelGGL((estep_backward_kernel<32, 1>), g, b, 0, st, a);
+  else if (a.mode == SPM_ESTEP_PARITY && a.lanemap)
+    hipLaunchKernelGGL((estep_backward_kernel<16, 4, kParityRoll | kBwdAT>), g, b, 0, st, a);
+  else if (a.mode == SPM_ESTEP_PARITY)
+    hipLaunchKernelGGL((estep_backward_kernel<16, 4, kParityRoll>), g, b, 0, st, a);
+  else if (a.lanemap)
+    hipLaunchKernelGGL((estep_backward_kernel<16, 3, kBwdRoll | kBwdAT>), g, b, 0, st, a);
+  else
+    hipLaunchKernelGGL((estep_backward_kernel<16, 3, kBwdRoll>), g, b, 0, st, a);
+}
 }  // namespace
 }  // namespace spm_amd
 
@@ -2368,11 +2133,6 @@ int spm_hip_estep_accumulate(spm_hip_pieces *P, const uint8_t *d_bytes, const ui
     a.flagged = P->w_flag.as<uint32_t>();
     a.status = P->w_status.as<uint32_t>();
     a.mode = mode;
-    static const int kNtRecords = [] {
-      const char *e = std::getenv("SPM_HIP_ESTEP_NT");
-      return e ? std::atoi(e) : 0;
-    }();
-    a.nt = kNtRecords;
     a.T = std::max(T, 1);
     a.index_base = index_base + c0 * index_stride;
     a.index_stride = index_stride;
@@ -2405,9 +2165,8 @@ int spm_hip_estep_accumulate(spm_hip_pieces *P, const uint8_t *d_bytes, const ui
       E_TRY(P->w_ectl.Reserve(256));
       E_TRY(hipMemsetAsync(P->w_ectl.ptr, 0, 256, st));
       EStepForwardOut eo{a.A, a.Zlat, a.N, a.ntok, a.flagged, a.status};
-      const EStepKnobs &kn = Knobs();
       // (The backward kernels that read AT are the rolled ones.)
-      if (kn.transposed_alpha && kn.roll && !(mode == SPM_ESTEP_PARITY && kn.stage) && P->ring_width == 16) {
+      if (P->ring_width == 16) {
         const uint64_t tiles = (cn + kEBlock - 1) / kEBlock;
         E_TRY(P->w_AT.Reserve(tiles * kATRows * kEBlock * 4));
         E_TRY(P->w_lanemap.Reserve(tiles * kEBlock));
@@ -2455,17 +2214,7 @@ int spm_hip_estep_accumulate(spm_hip_pieces *P, const uint8_t *d_bytes, const ui
     uint64_t total_rec = 0;
     if (mode == SPM_ESTEP_PARITY) {
       // rec_off = exclusive scan of N.
-      size_t tb = 0;
-      hipcub::TransformInputIterator<uint64_t, ToU64E, const uint32_t *> it(a.N, ToU64E());
-      E_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, it, P->w_recoff.as<uint64_t>() + 1,
-                                             static_cast<int>(cn), st));
-      E_TRY(P->w_tmp.Reserve(tb + 16));
-      E_TRY(hipMemsetAsync(P->w_recoff.ptr, 0, 8, st));
-      E_TRY(hipcub::DeviceScan::InclusiveSum(P->w_tmp.ptr, tb, it, P->w_recoff.as<uint64_t>() + 1,
-                                             static_cast<int>(cn), st));
-      E_TRY(hipMemcpyAsync(P->pinned + 4, P->w_recoff.as<uint64_t>() + cn, 8, hipMemcpyDeviceToHost, st));
-      E_TRY(hipStreamSynchronize(st));
-      std::memcpy(&total_rec, P->pinned + 4, 8);
+      if (const int rc = ScanCounts(P, a.N, cn, P->w_recoff.as<uint64_t>(), P->pinned + 4, st, &total_rec)) return rc;
       if (total_rec >= (1ull << 31)) return Err(P, SPM_RESOURCE_EXHAUSTED, "too many lattice nodes in a chunk");
       const uint64_t nrec = std::max<uint64_t>(total_rec, 1);
       E_TRY(P->w_keys.Reserve(nrec * 4));
@@ -2496,54 +2245,21 @@ int spm_hip_estep_accumulate(spm_hip_pieces *P, const uint8_t *d_bytes, const ui
         E_TRY(hipMemcpyAsync(P->w_kept.ptr, a.N, cn * 4, hipMemcpyDeviceToDevice, st));
         a.drop_exp = P->w_drop.as<uint8_t>();
         a.kept = P->w_kept.as<uint32_t>();
-        // Deferred record values (SPM_HIP_ESTEP_DEFER=0: off, A/B knob).
-        static const bool kDefer = [] {
-          const char *e = std::getenv("SPM_HIP_ESTEP_DEFER");
-          return !(e && std::atoi(e) == 0);
-        }();
-        if (kDefer) a.exs = reinterpret_cast<float *>(a.vals);
+        // Deferred record values, in the vals buffer's storage.
+        a.exs = reinterpret_cast<float *>(a.vals);
       }
     }
     ETimingMark(P, st);  // backward pass begins
     if (ring_ok) {
       const unsigned bblocks = std::min<unsigned>(blocks, 2048);  // LDS accumulators flushed per block
-      if (P->ring_width == 16) {
-        // PARITY calls: the PARITY-only lagged kernel (no FAST LDS table: 121
-        // VGPRs, 14 KB LDS, 4 waves/SIMD; 0.524 -> 0.510 s/epoch at c4,
-        // profiles/r02za_estep_bwd_ab.txt).  FAST keeps the batched kernel (the
-        // lagged one is slower there: 0.315 vs 0.299 s/epoch, the emit work
-        // sits between dependent walk steps).
-        const EStepKnobs &kn = Knobs();
-        if (mode == SPM_ESTEP_PARITY) {
-          if (a.lanemap) {  // the forward pass wrote AT (kn.roll, !kn.stage)
-            if (kn.transposed_records && a.exs) {
-              const uint64_t tiles = (cn + kEBlock - 1) / kEBlock;
-              E_TRY(P->w_RT.Reserve(tiles * kRTRows * kEBlock * 8));
-              a.RT = P->w_RT.as<uint2>();
-              a.rt_rows = kRTRows;
-            }
-            hipLaunchKernelGGL((estep_backward_kernel<16, 4, 42>), dim3(bblocks), dim3(kEBlock), 0, st, a);
-          } else if (kn.roll && kn.stage)
-            hipLaunchKernelGGL((estep_backward_kernel<16, 4, 26>), dim3(bblocks), dim3(kEBlock), 0, st, a);
-          else if (kn.roll)
-            hipLaunchKernelGGL((estep_backward_kernel<16, 4, 10>), dim3(bblocks), dim3(kEBlock), 0, st, a);
-          else if (kn.pair)
-            hipLaunchKernelGGL((estep_backward_kernel<16, 3, 6>), dim3(bblocks), dim3(kEBlock), 0, st, a);
-          else
-            hipLaunchKernelGGL((estep_backward_kernel<16, 4, 3>), dim3(bblocks), dim3(kEBlock), 0, st, a);
-        } else {
-          if (a.lanemap)
-            hipLaunchKernelGGL((estep_backward_kernel<16, 3, 40>), dim3(bblocks), dim3(kEBlock), 0, st, a);
-          else if (kn.roll)
-            hipLaunchKernelGGL((estep_backward_kernel<16, 3, 8>), dim3(bblocks), dim3(kEBlock), 0, st, a);
-          else if (kn.pair)
-            hipLaunchKernelGGL((estep_backward_kernel<16, 3, 4>), dim3(bblocks), dim3(kEBlock), 0, st, a);
-          else
-            hipLaunchKernelGGL((estep_backward_kernel<16, 3>), dim3(bblocks), dim3(kEBlock), 0, st, a);
-        }
-      } else {
-        hipLaunchKernelGGL((estep_backward_kernel<32, 1>), dim3(bblocks), dim3(kEBlock), 0, st, a);
+      // Deferred records tile-transposed (the AT kernel's lanes own the columns).
+      if (mode == SPM_ESTEP_PARITY && a.lanemap && a.exs) {
+        const uint64_t tiles = (cn + kEBlock - 1) / kEBlock;
+        E_TRY(P->w_RT.Reserve(tiles * kRTRows * kEBlock * 8));
+        a.RT = P->w_RT.as<uint2>();
+        a.rt_rows = kRTRows;
       }
+      LaunchEStepBackward(P->ring_width, bblocks, st, a);
       E_TRY(hipGetLastError());
     }
     ETimingMark(P, st);  // backward pass ends
@@ -2570,30 +2286,19 @@ int spm_hip_estep_accumulate(spm_hip_pieces *P, const uint8_t *d_bytes, const ui
       const double *sort_vals = a.vals;
       uint64_t nsort = total_rec;
       if (a.kept) {
-        size_t tb = 0;
-        hipcub::TransformInputIterator<uint64_t, ToU64E, const uint32_t *> it(a.kept, ToU64E());
         E_TRY(P->w_koff.Reserve((cn + 1) * 8));
-        E_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, it, P->w_koff.as<uint64_t>() + 1, static_cast<int>(cn),
-                                               st));
-        E_TRY(P->w_tmp.Reserve(tb + 16));
-        E_TRY(hipMemsetAsync(P->w_koff.ptr, 0, 8, st));
-        E_TRY(hipcub::DeviceScan::InclusiveSum(P->w_tmp.ptr, tb, it, P->w_koff.as<uint64_t>() + 1,
-                                               static_cast<int>(cn), st));
-        E_TRY(hipMemcpyAsync(P->pinned + 8, P->w_koff.as<uint64_t>() + cn, 8, hipMemcpyDeviceToHost, st));
-        E_TRY(hipStreamSynchronize(st));
-        std::memcpy(&nsort, P->pinned + 8, 8);
+        if (const int rc = ScanCounts(P, a.kept, cn, P->w_koff.as<uint64_t>(), P->pinned + 8, st, &nsort)) return rc;
         if (nsort > total_rec) return Err(P, SPM_INTERNAL, "E-step record drop: kept more records than written");
-        if (nsort < total_rec || a.exs) {
-          E_TRY(P->w_ckeys.Reserve(std::max<uint64_t>(nsort, 1) * 4));
-          E_TRY(P->w_cvals.Reserve(std::max<uint64_t>(nsort, 1) * 8));
-          hipLaunchKernelGGL(estep_compact_records_kernel, dim3(static_cast<unsigned>((cn + 255) / 256)), dim3(256),
-                             0, st, cn, a.rec_off, a.N, a.kept, P->w_koff.as<uint64_t>(), a.keys, a.vals, a.exs,
-                             a.freq, P->w_ckeys.as<uint32_t>(), P->w_cvals.as<double>(), a.RT,
-                             P->w_colmap.as<uint16_t>(), a.rt_rows);
-          E_TRY(hipGetLastError());
-          sort_keys = P->w_ckeys.as<uint32_t>();
-          sort_vals = P->w_cvals.as<double>();
-        }
+        // The kept records densely, with their deferred values computed.
+        E_TRY(P->w_ckeys.Reserve(std::max<uint64_t>(nsort, 1) * 4));
+        E_TRY(P->w_cvals.Reserve(std::max<uint64_t>(nsort, 1) * 8));
+        hipLaunchKernelGGL(estep_compact_records_kernel, dim3(static_cast<unsigned>((cn + 255) / 256)), dim3(256), 0,
+                           st, cn, a.rec_off, a.N, a.kept, P->w_koff.as<uint64_t>(), a.keys, a.vals, a.exs, a.freq,
+                           P->w_ckeys.as<uint32_t>(), P->w_cvals.as<double>(), a.RT, P->w_colmap.as<uint16_t>(),
+                           a.rt_rows);
+        E_TRY(hipGetLastError());
+        sort_keys = P->w_ckeys.as<uint32_t>();
+        sort_vals = P->w_cvals.as<double>();
       }
       P->rec_total += total_rec;
       P->rec_kept += nsort;

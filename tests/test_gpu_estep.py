@@ -45,8 +45,8 @@ def _corpus(n, seed):
 FORWARDS = [1, 2]
 
 
-def _assert_exact(sents, freqs, pieces, scores, threads, forward=0):
-    e_ref, obj_ref, nt_ref = O.estep(sents, freqs, pieces, scores, threads)
+def _assert_exact(sents, freqs, pieces, scores, threads, forward=0, ref=None):
+    e_ref, obj_ref, nt_ref = ref if ref is not None else O.estep(sents, freqs, pieces, scores, threads)
     dp = S.DevicePieces(pieces, scores)
     dp.set_forward(forward)
     e, obj, nt = dp.estep(sents, freqs, mode=S.SPM_ESTEP_PARITY, threads=threads)
@@ -154,6 +154,25 @@ def test_estep_parity_long_pieces(threads):
     _assert_exact(sents, freqs, pieces, scores, threads)
 
 
+def test_estep_ring32_both_modes():
+    """Pieces of 16-31 chars take the W = 32 ring, whose backward kernel emits per
+    depth and serves both modes: PARITY bit-exact at T = 1 and 8, FAST within
+    test_estep_fast_mode's bounds.  (The pieces are 21 mostly-ASCII chars, well
+    under the walk's 64-byte limit, so the ring kernels run, not the general one.)"""
+    pieces, scores, sents, freqs = _long_piece_set(20, 13)
+    chars = [len(p.decode()) for p in pieces]
+    assert 16 <= max(chars) < 32, max(chars)
+    ref1 = O.estep(sents, freqs, pieces, scores, 1)
+    _assert_exact(sents, freqs, pieces, scores, 1, ref=ref1)
+    _assert_exact(sents, freqs, pieces, scores, 8)
+    e_ref, obj_ref, nt_ref = ref1
+    e, obj, nt = S.DevicePieces(pieces, scores).estep(sents, freqs, mode=S.SPM_ESTEP_FAST)
+    assert nt == nt_ref
+    rel = _check_close(e, e_ref)
+    assert rel < 1e-3, rel
+    assert abs(obj - obj_ref) <= 1e-4 * abs(obj_ref)
+
+
 def test_estep_parity_long_multibyte_walks():
     """Pieces of 22-31 CJK chars (66-93 bytes): the W = 32 ring's trie walks go
     past the 64-byte char-end mask and must take the general kernel."""
@@ -179,8 +198,9 @@ def test_estep_parity_unk_id_collision(threads, forward):
     With a multi-char piece 0 ("ab") and no single-char piece for 'a', a lattice position
     holds both the trie node of piece 0 and the UNK node (id 0 too): their two records share
     one key, so they must reach the fold in begin_nodes order (trie nodes, then UNK).  The
-    lagged PARITY backward kernel writes a position's records from the block's end and
-    reserves the UNK slot last; this pins that order bit-exactly."""
+    rolled PARITY backward kernel writes a position's records downwards from the end of
+    the sentence's range, UNK's first, so it sits above the trie nodes' ones; this pins
+    that order bit-exactly."""
     rng = np.random.default_rng(21)
     pieces = [p.encode() for p in ["ab", "b", "c", "bc", "abc", "cab", "▁", "▁ab", "ca"]]
     scores = np.array([-1.5, -2.0, -2.5, -3.0, -3.5, -4.0, -1.0, -2.25, -2.75], dtype=np.float32)
