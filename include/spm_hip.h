@@ -1033,6 +1033,67 @@ int spm_hip_count_ids(spm_hip_model *model, const int32_t *d_ids, uint64_t num_t
 int spm_hip_count_ids_host(spm_hip_model *model, const int32_t *ids, uint64_t num_tokens, uint64_t *counts,
                            uint32_t *status);
 
+/* Dense id batches: a final id CSR on the device as the rectangular int32
+ * tensor a training or inference loop on the same GPU takes, without a trip
+ * to the host.  No reference counterpart (the reference returns one
+ * std::vector<int> per sentence).  DEVICE pointers: d_ids / d_offsets[n+1] as
+ * produced by spm_hip_encode_batch or spm_hip_finalize_ids; the offsets index
+ * d_ids and need not start at 0.  row_len = L.  Any int32 is a legal pad_id
+ * (the model's own pad id is -1 unless trained otherwise; -100 is a common
+ * label filler).
+ *
+ * Pad: one sentence per row.  len = offsets[i+1] - offsets[i], k = min(len, L).
+ * Tokens [0, k) go to columns [0, k) and pad_id to [k, L).  Flags:
+ *   SPM_DENSE_PAD_LEFT       the tokens go to columns [L-k, L), the pads in front
+ *   SPM_DENSE_TRUNCATE_LEFT  tokens [len-k, len) are kept
+ *   SPM_DENSE_KEEP_END       a sentence that is cut keeps its outermost token on
+ *                            the cut side: cut on the right, the last kept slot
+ *                            holds token len-1; cut on the left, the first kept
+ *                            slot holds token 0.  A bos / eos of the extra
+ *                            options survives; L = 1 is legal and gives that token
+ * Outputs: d_out[n*L]; nullable d_lengths[n] (int32, = k), d_mask[n*L] (uint8,
+ * 1 on token slots) and d_stats[2] (uint64: sentences cut, tokens dropped).  An
+ * empty sentence gives a row of pads with length 0.
+ *
+ * Pack: the LM-pretraining layout.  The sentences' ids run on, in order, as
+ * one stream of T = offsets[n] - offsets[0] slots; slot t stands in row t / L,
+ * column t % L, and the rest of the last row holds pad_id.  Empty sentences
+ * contribute nothing.  Outputs: d_out[rows_capacity*L]; nullable d_seq (int32
+ * per slot: the index i of the slot's sentence, -1 on padding), d_pos (int32
+ * per slot: t - (offsets[i] - offsets[0]), which keeps counting where a
+ * sentence crosses a row edge; 0 on padding) and d_stats[2] (uint64: rows
+ * needed = ceil(T / L), T).  Rows beyond rows_capacity are not written and
+ * rows between ceil(T / L) and rows_capacity are not touched, so a caller who
+ * sized by d_stats[0], or by the total spm_hip_finalize_ids returns, gets
+ * exactly its rows.  Packing whole sentences into rows without splitting them
+ * (bin packing) is out of scope.
+ *
+ * The device calls are pure stream calls in the sense of the _async entries:
+ * they allocate nothing, do not synchronize and read nothing back, and every
+ * failure is an argument check on the host before anything is enqueued.  They
+ * take no model handle (they need no workspace), so any stream will do.
+ * SPM_INVALID_ARGUMENT: row_len == 0 or > INT32_MAX, a null d_out or
+ * d_offsets, an unknown flag bit.  SPM_OUT_OF_RANGE: pack with n > INT32_MAX
+ * (seq is int32); pad with n * row_len past 64 bits.  n == 0 is fine: no
+ * output slot is written and d_stats = {0, 0}.  The _host forms take host
+ * pointers, run the same per-slot rule in a plain loop on the calling thread
+ * and never touch the GPU. */
+#define SPM_DENSE_PAD_LEFT 0x1u
+#define SPM_DENSE_TRUNCATE_LEFT 0x2u
+#define SPM_DENSE_KEEP_END 0x4u
+int spm_hip_pad_ids(const int32_t *d_ids, const uint64_t *d_offsets, uint64_t n, uint32_t row_len,
+                    int32_t pad_id, uint32_t flags, int32_t *d_out, int32_t *d_lengths, uint8_t *d_mask,
+                    uint64_t *d_stats, void *stream);
+int spm_hip_pack_ids(const int32_t *d_ids, const uint64_t *d_offsets, uint64_t n, uint32_t row_len,
+                     int32_t pad_id, uint64_t rows_capacity, int32_t *d_out, int32_t *d_seq, int32_t *d_pos,
+                     uint64_t *d_stats, void *stream);
+int spm_hip_pad_ids_host(const int32_t *ids, const uint64_t *offsets, uint64_t n, uint32_t row_len,
+                         int32_t pad_id, uint32_t flags, int32_t *out, int32_t *lengths, uint8_t *mask,
+                         uint64_t *stats);
+int spm_hip_pack_ids_host(const int32_t *ids, const uint64_t *offsets, uint64_t n, uint32_t row_len,
+                          int32_t pad_id, uint64_t rows_capacity, int32_t *out, int32_t *seq, int32_t *pos,
+                          uint64_t *stats);
+
 /* Device memory this library holds in the calling process (every block it
  * allocates: models' workspaces, E-step piece sets, trainer corpus and
  * scratch): live bytes now and the high-water mark since the last reset.

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <fstream>
 #include <iterator>
+#include <limits>
 #include <random>
 #include <sstream>
 
@@ -377,7 +378,10 @@ Status SentencePieceProcessor::SampleEncode(const std::string &input, int nbest_
 }
 
 namespace {
-enum { kIn, kInOff, kNorm, kNormOff, kIds, kLen, kTok, kOut, kOutOff, kSmallBlockSlot, kCounts };
+enum {
+  kIn, kInOff, kNorm, kNormOff, kIds, kLen, kTok, kOut, kOutOff, kSmallBlockSlot, kCounts,
+  kDenseIds, kDenseAux0, kDenseAux1, kDenseStats
+};
 }  // namespace
 
 // CalculateEntropy of the `sentencepiece` package, batched: the device
@@ -673,6 +677,118 @@ Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, 
       for (auto &p : spt) (*pieces)[i].push_back(std::move(p.first));
   }
   return Status::Ok();
+}
+
+// Dense id batches: the final id CSR of the batch (device encode + device id
+// epilogue; WORD / CHAR: RunBatch's host epilogue, uploaded) through
+// spm_hip_pad_ids / spm_hip_pack_ids into dev_'s buffers.
+Status SentencePieceProcessor::RunDense(const std::vector<std::string> &inputs, const SampleSpec *sample,
+                                        const DenseOptions &o, DenseBatch *out,
+                                        std::vector<int32_t> *host_ids) const {
+  if (!status_.ok()) return status_;
+  if (host_only_) return Err(SPM_FAILED_PRECONDITION, "host-only processor");
+  if (!out) return Err(SPM_INTERNAL, "output container is null");
+  if (o.row_len == 0 || o.row_len > 0x7FFFFFFFu) return Err(SPM_INVALID_ARGUMENT, "row_len must be in [1, INT32_MAX]");
+  if (o.flags & ~(o.pack ? 0u : SPM_DENSE_PAD_LEFT | SPM_DENSE_TRUNCATE_LEFT | SPM_DENSE_KEEP_END))
+    return Err(SPM_INVALID_ARGUMENT, "unknown dense flag bit");
+  *out = DenseBatch();
+  out->row_len = o.row_len;
+  if (host_ids) host_ids->clear();
+  const uint64_t n = inputs.size(), L = o.row_len;
+  if (n == 0) return Status::Ok();
+  auto fail_hip = [](hipError_t e) { return Err(SPM_INTERNAL, hipGetErrorString(e)); };
+  hipError_t he;
+  int32_t *d_csr = nullptr;
+  uint64_t *d_csr_off = nullptr;
+  uint64_t fin = 0;
+  const bool word_char = proto_.trainer_spec.model_type == kWord || proto_.trainer_spec.model_type == kChar;
+  if (word_char) {
+    std::vector<std::vector<int>> rows;
+    Status st = RunBatch(inputs, &rows, nullptr, sample);
+    if (!st.ok()) return st;
+    std::vector<uint64_t> off(n + 1, 0);
+    std::vector<int32_t> flat;
+    for (uint64_t i = 0; i < n; ++i) {
+      flat.insert(flat.end(), rows[i].begin(), rows[i].end());
+      off[i + 1] = flat.size();
+    }
+    fin = flat.size();
+    d_csr_off = static_cast<uint64_t *>(dev_.Get(kOutOff, (n + 1) * 8));
+    d_csr = static_cast<int32_t *>(dev_.Get(kOut, std::max<uint64_t>(fin, 1) * 4));
+    if (!d_csr_off || !d_csr) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+    if ((he = hipMemcpy(d_csr_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess ||
+        (fin && (he = hipMemcpy(d_csr, flat.data(), fin * 4, hipMemcpyHostToDevice)) != hipSuccess))
+      return fail_hip(he);
+  } else {
+    DeviceBatch b;
+    Status st = DeviceEncode(inputs, sample, &b);
+    if (!st.ok()) return st;
+    st = DeviceFinalize(b, n, &d_csr, &d_csr_off, &fin);
+    if (!st.ok()) return st;
+  }
+  // Pack: the row count comes from the id count the epilogue returned.
+  const uint64_t rows = o.pack ? (fin + L - 1) / L : n;
+  if (rows > std::numeric_limits<uint64_t>::max() / (4 * L)) return Err(SPM_OUT_OF_RANGE, "rows * row_len is too large");
+  const uint64_t slots = rows * L;
+  int32_t *d_ids = static_cast<int32_t *>(dev_.Get(kDenseIds, slots * 4));
+  void *d_a0 = dev_.Get(kDenseAux0, o.pack ? slots * 4 : n * 4);  // seq | lengths
+  void *d_a1 = dev_.Get(kDenseAux1, o.pack ? slots * 4 : slots);  // pos | mask
+  uint64_t *d_stats = static_cast<uint64_t *>(dev_.Get(kDenseStats, 16));
+  if (!d_ids || !d_a0 || !d_a1 || !d_stats) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+  Status st = FromC(o.pack ? spm_hip_pack_ids(d_csr, d_csr_off, n, o.row_len, o.pad_id, rows, d_ids,
+                                              static_cast<int32_t *>(d_a0), static_cast<int32_t *>(d_a1), d_stats,
+                                              nullptr)
+                           : spm_hip_pad_ids(d_csr, d_csr_off, n, o.row_len, o.pad_id, o.flags, d_ids,
+                                             static_cast<int32_t *>(d_a0), static_cast<uint8_t *>(d_a1), d_stats,
+                                             nullptr));
+  if (!st.ok()) return st;
+  out->ids = d_ids;
+  (o.pack ? out->seq : out->lengths) = static_cast<const int32_t *>(d_a0);
+  if (o.pack) out->pos = static_cast<const int32_t *>(d_a1);
+  else out->mask = static_cast<const uint8_t *>(d_a1);
+  out->stats = d_stats;
+  out->rows = rows;
+  out->tokens = fin;
+  if (host_ids) {
+    host_ids->resize(slots);
+    uint64_t stats[2] = {0, 0};
+    if ((slots && (he = hipMemcpy(host_ids->data(), d_ids, slots * 4, hipMemcpyDeviceToHost)) != hipSuccess) ||
+        (he = hipMemcpy(stats, d_stats, 16, hipMemcpyDeviceToHost)) != hipSuccess)
+      return fail_hip(he);
+    if (!o.pack) {
+      out->cut = stats[0];
+      out->dropped = stats[1];
+    }
+  }
+  return Status::Ok();
+}
+
+Status SentencePieceProcessor::EncodeDense(const std::vector<std::string> &inputs, const DenseOptions &options,
+                                           DenseBatch *out, std::vector<int32_t> *host_ids) const {
+  return RunDense(inputs, nullptr, options, out, host_ids);
+}
+
+Status SentencePieceProcessor::SampleEncodeDense(const std::vector<std::string> &inputs, int nbest_size, float alpha,
+                                                 const DenseOptions &options, DenseBatch *out,
+                                                 std::vector<int32_t> *host_ids) const {
+  if (!status_.ok()) return status_;
+  // The rules of SampleEncodeBatch.
+  if (nbest_size > 512) return Err(SPM_INTERNAL, "nbest_size must be nbest_size <= 512");
+  if (nbest_size == 0 || nbest_size == 1) return RunDense(inputs, nullptr, options, out, host_ids);
+  const bool bpe = proto_.trainer_spec.model_type == kBpe;
+  if (nbest_size > 1 && !bpe)
+    return Err(SPM_UNIMPLEMENTED,
+               "SampleEncode among the n best (nbest_size > 1) is not implemented on the device; "
+               "use nbest_size=-1 to sample from the whole lattice");
+  if (!sample_seeded_) {
+    std::random_device rd;
+    sample_seed_ = (static_cast<uint64_t>(rd()) << 32) | rd();
+    sample_seeded_ = true;
+  }
+  const SampleSpec spec{alpha, sample_seed_, sample_count_};
+  Status st = RunDense(inputs, &spec, options, out, host_ids);
+  if (st.ok()) sample_count_ += inputs.size();
+  return st;
 }
 
 // SetVocabulary / ResetVocabulary / LoadVocabulary (sentencepiece_processor.cc:

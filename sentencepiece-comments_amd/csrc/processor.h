@@ -140,6 +140,47 @@ class SentencePieceProcessor {
   Status ResetVocabulary();
   Status LoadVocabulary(const std::string &filename, int threshold);
 
+  // Dense id batches: Encode (or SampleEncode) of every line, then the final
+  // ids as one rectangular int32 tensor that stays on the device
+  // (spm_hip_pad_ids / spm_hip_pack_ids), for a training or inference loop on
+  // the same GPU.  pack = false: one line per row, padded with pad_id or cut
+  // to row_len (flags: SPM_DENSE_PAD_LEFT, SPM_DENSE_TRUNCATE_LEFT,
+  // SPM_DENSE_KEEP_END).  pack = true: the lines' ids run on as one stream of
+  // row_len slots per row (flags must be 0).  The extra options are part of
+  // the ids, so they apply before padding.
+  struct DenseOptions {
+    uint32_t row_len = 0;
+    int32_t pad_id = 0;
+    uint32_t flags = 0;
+    bool pack = false;
+  };
+  // Device pointers, owned by the processor and valid until the next call on
+  // the instance; the work that fills them is enqueued on the null stream.
+  struct DenseBatch {
+    const int32_t *ids = nullptr;      // [rows, row_len]
+    const int32_t *lengths = nullptr;  // pad: [rows], tokens kept per row
+    const uint8_t *mask = nullptr;     // pad: [rows, row_len], 1 on token slots
+    const int32_t *seq = nullptr;      // pack: [rows, row_len], the slot's line, -1 on padding
+    const int32_t *pos = nullptr;      // pack: [rows, row_len], the slot's position in its line
+    const uint64_t *stats = nullptr;   // pad: {lines cut, tokens dropped}; pack: {rows, tokens}
+    uint64_t rows = 0;                 // pad: the lines; pack: ceil(tokens / row_len)
+    uint32_t row_len = 0;
+    uint64_t tokens = 0;  // final ids of the batch before padding
+    // Only with host_ids (the call then waits for the device): the stats of pad.
+    uint64_t cut = 0, dropped = 0;
+  };
+  // Nothing but the id count comes back to the host unless host_ids is given
+  // (then it receives the rows * row_len ids).  A WORD or CHAR model takes its
+  // host id epilogue as in Encode; the ids go back up and through the same
+  // kernel.  A host-only processor gives SPM_FAILED_PRECONDITION.
+  Status EncodeDense(const std::vector<std::string> &inputs, const DenseOptions &options, DenseBatch *out,
+                     std::vector<int32_t> *host_ids = nullptr) const;
+  // SampleEncodeBatch in place of the encode: the same seed rules, the same
+  // advance of the sentence counter and the same refusals for nbest_size.
+  Status SampleEncodeDense(const std::vector<std::string> &inputs, int nbest_size, float alpha,
+                           const DenseOptions &options, DenseBatch *out,
+                           std::vector<int32_t> *host_ids = nullptr) const;
+
   // counts[id] += the occurrences of id in Encode(line, &ids) of every input
   // line (extra options applied; counts grows to GetPieceSize()).  Normalize,
   // encode, id epilogue and count run on the device (spm_hip_count_ids); only
@@ -245,6 +286,9 @@ class SentencePieceProcessor {
   Status DeviceNormalize(const std::vector<std::string> &inputs, uint8_t **d_norm, uint64_t **d_norm_off,
                          uint64_t *total) const;
   Status DeviceFinalize(const DeviceBatch &b, uint64_t n, int32_t **d_out, uint64_t **d_out_off, uint64_t *fin) const;
+  // EncodeDense / SampleEncodeDense.
+  Status RunDense(const std::vector<std::string> &inputs, const SampleSpec *sample, const DenseOptions &options,
+                  DenseBatch *out, std::vector<int32_t> *host_ids) const;
   // EncodeBatch; with `sample` the device sampler stands in for the encode.
   Status RunBatch(const std::vector<std::string> &inputs, std::vector<std::vector<int>> *ids,
                   std::vector<std::vector<std::string>> *pieces, const SampleSpec *sample) const;
@@ -253,8 +297,8 @@ class SentencePieceProcessor {
                       uint64_t count, std::vector<std::pair<std::string, int>> *out) const;
   // Grow-only device staging for EncodeBatch (raw lines → normalized → ids).
   struct Staging {
-    void *ptr[11] = {};
-    size_t cap[11] = {};
+    void *ptr[15] = {};
+    size_t cap[15] = {};
     void *Get(int k, size_t bytes);
     ~Staging();
   };

@@ -19,6 +19,7 @@
 
 #include "../../include/spm_hip.h"
 #include "bpe_tables.h"
+#include "dense.h"
 #include "device_model.h"
 #include "epilogue.h"
 #include "host_nbest.h"
@@ -3835,6 +3836,78 @@ int spm_hip_count_ids_host(spm_hip_model *m, const int32_t *ids, uint64_t num_to
   SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, d_status, 4, hipMemcpyDeviceToHost, st));
   SPM_HIP_TRY(hipStreamSynchronize(st));
   if (status) *status = ws->pinned[0];
+  return SPM_OK;
+}
+
+// ---- Dense id batches (dense.h) ----
+
+namespace {
+
+// The argument checks the device and the host entries share; nothing here
+// touches HIP.
+int DenseArgs(const uint64_t *off, uint32_t row_len, uint32_t flags, const int32_t *out) {
+  if (!off || !out) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (row_len == 0 || row_len > 0x7FFFFFFFu) return Fail(SPM_INVALID_ARGUMENT, "row_len must be in [1, INT32_MAX]");
+  if (flags & ~spm_amd::kDenseFlagMask) return Fail(SPM_INVALID_ARGUMENT, "unknown dense flag bit");
+  return SPM_OK;
+}
+
+int PadArgs(const uint64_t *off, uint64_t n, uint32_t row_len, uint32_t flags, const int32_t *out) {
+  const int rc = DenseArgs(off, row_len, flags, out);
+  if (rc != SPM_OK) return rc;
+  if (n > std::numeric_limits<uint64_t>::max() / row_len) return Fail(SPM_OUT_OF_RANGE, "n * row_len exceeds 64 bits");
+  return SPM_OK;
+}
+
+int PackArgs(const uint64_t *off, uint64_t n, uint32_t row_len, const int32_t *out, uint64_t *rows_capacity) {
+  const int rc = DenseArgs(off, row_len, 0, out);
+  if (rc != SPM_OK) return rc;
+  if (n > 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  // More rows than 64-bit slots cannot be written anyway.
+  *rows_capacity = std::min(*rows_capacity, std::numeric_limits<uint64_t>::max() / row_len);
+  return SPM_OK;
+}
+
+}  // namespace
+
+int spm_hip_pad_ids(const int32_t *d_ids, const uint64_t *d_off, uint64_t n, uint32_t row_len, int32_t pad_id,
+                    uint32_t flags, int32_t *d_out, int32_t *d_lengths, uint8_t *d_mask, uint64_t *d_stats,
+                    void *stream) {
+  const int rc = PadArgs(d_off, n, row_len, flags, d_out);
+  if (rc != SPM_OK) return rc;
+  spm_amd::TraceRange trace_range_("spm_hip_pad_ids");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (d_stats) SPM_HIP_TRY(hipMemsetAsync(d_stats, 0, 2 * sizeof(uint64_t), st));
+  SPM_HIP_TRY(spm_amd::LaunchDensePad(d_ids, d_off, n, row_len, pad_id, flags, d_out, d_lengths, d_mask, d_stats, st));
+  return SPM_OK;
+}
+
+int spm_hip_pack_ids(const int32_t *d_ids, const uint64_t *d_off, uint64_t n, uint32_t row_len, int32_t pad_id,
+                     uint64_t rows_capacity, int32_t *d_out, int32_t *d_seq, int32_t *d_pos, uint64_t *d_stats,
+                     void *stream) {
+  const int rc = PackArgs(d_off, n, row_len, d_out, &rows_capacity);
+  if (rc != SPM_OK) return rc;
+  spm_amd::TraceRange trace_range_("spm_hip_pack_ids");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (n == 0 && d_stats) SPM_HIP_TRY(hipMemsetAsync(d_stats, 0, 2 * sizeof(uint64_t), st));
+  SPM_HIP_TRY(spm_amd::LaunchDensePack(d_ids, d_off, n, row_len, pad_id, rows_capacity, d_out, d_seq, d_pos, d_stats,
+                                       st));
+  return SPM_OK;
+}
+
+int spm_hip_pad_ids_host(const int32_t *ids, const uint64_t *off, uint64_t n, uint32_t row_len, int32_t pad_id,
+                         uint32_t flags, int32_t *out, int32_t *lengths, uint8_t *mask, uint64_t *stats) {
+  const int rc = PadArgs(off, n, row_len, flags, out);
+  if (rc != SPM_OK) return rc;
+  spm_amd::DensePadHostLoop(ids, off, n, row_len, pad_id, flags, out, lengths, mask, stats);
+  return SPM_OK;
+}
+
+int spm_hip_pack_ids_host(const int32_t *ids, const uint64_t *off, uint64_t n, uint32_t row_len, int32_t pad_id,
+                          uint64_t rows_capacity, int32_t *out, int32_t *seq, int32_t *pos, uint64_t *stats) {
+  const int rc = PackArgs(off, n, row_len, out, &rows_capacity);
+  if (rc != SPM_OK) return rc;
+  spm_amd::DensePackHostLoop(ids, off, n, row_len, pad_id, rows_capacity, out, seq, pos, stats);
   return SPM_OK;
 }
 

@@ -57,7 +57,12 @@ EXPORTED = [
     "spm_hip_model_set_piece_types", "spm_hip_model_get_piece_types", "spm_hip_model_set_vocabulary",
     "spm_hip_model_reset_vocabulary", "spm_hip_count_ids", "spm_hip_count_ids_host",
     "spm_hip_model_byte_fallback", "spm_hip_finalize_ids_bytes", "spm_hip_finalize_ids_bytes_async",
+    "spm_hip_pad_ids", "spm_hip_pack_ids", "spm_hip_pad_ids_host", "spm_hip_pack_ids_host",
 ]
+# Flags of spm_hip_pad_ids (include/spm_hip.h).
+SPM_DENSE_PAD_LEFT, SPM_DENSE_TRUNCATE_LEFT, SPM_DENSE_KEEP_END = 1, 2, 4
+# Dense kernels (csrc/dense.h): blocks of a pad / pack launch and slots a block covers per step.
+DENSE_BLOCKS, DENSE_PACK_BLOCKS, DENSE_TILE_SLOTS = 1024, 2048, 1024
 
 ABI_VERSION = 3  # SPM_HIP_ABI_VERSION of include/spm_hip.h (struct layouts below)
 
@@ -260,6 +265,11 @@ def lib():
         L.spm_hip_model_reset_vocabulary.argtypes = [P]
         L.spm_hip_count_ids.argtypes = [P, P, U64, P, P, P]
         L.spm_hip_count_ids_host.argtypes = [P, P, U64, P, ctypes.POINTER(ctypes.c_uint32)]
+        U32 = ctypes.c_uint32
+        L.spm_hip_pad_ids.argtypes = [P, P, U64, U32, I32, U32, P, P, P, P, P]
+        L.spm_hip_pack_ids.argtypes = [P, P, U64, U32, I32, U64, P, P, P, P, P]
+        L.spm_hip_pad_ids_host.argtypes = [P, P, U64, U32, I32, U32, P, P, P, P]
+        L.spm_hip_pack_ids_host.argtypes = [P, P, U64, U32, I32, U64, P, P, P, P]
         _lib = L
     return _lib
 
@@ -307,6 +317,68 @@ def to_csr(items):
     if buf.size == 0:
         buf = np.zeros(1, dtype=np.uint8)
     return buf, off
+
+
+def _vp(x):
+    return ctypes.c_void_p(x) if x else None
+
+
+def pad_ids_device(d_ids, d_off, n, row_len, pad_id, flags, d_out, d_lengths=None, d_mask=None, d_stats=None,
+                   stream=None):
+    """spm_hip_pad_ids on device pointers (ints): a pure stream call, no model handle."""
+    _check(lib().spm_hip_pad_ids(_vp(d_ids), _vp(d_off), n, row_len, pad_id, flags, _vp(d_out), _vp(d_lengths),
+                                 _vp(d_mask), _vp(d_stats), _vp(stream)))
+
+
+def pack_ids_device(d_ids, d_off, n, row_len, pad_id, rows_capacity, d_out, d_seq=None, d_pos=None, d_stats=None,
+                    stream=None):
+    """spm_hip_pack_ids on device pointers (ints): a pure stream call, no model handle."""
+    _check(lib().spm_hip_pack_ids(_vp(d_ids), _vp(d_off), n, row_len, pad_id, rows_capacity, _vp(d_out), _vp(d_seq),
+                                  _vp(d_pos), _vp(d_stats), _vp(stream)))
+
+
+def _host_csr(ids, off):
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    return (ids if ids.size else np.zeros(1, dtype=np.int32)), off, len(off) - 1
+
+
+def pad_ids_host(ids, off, row_len, pad_id, flags=0, with_lengths=True, with_mask=True, with_stats=True):
+    """spm_hip_pad_ids_host on a numpy id CSR (no GPU): (out int32[n, L],
+    lengths int32[n], mask uint8[n, L], stats uint64[2]); an output that is
+    not asked for is passed as NULL and returned as None."""
+    ids, off, n = _host_csr(ids, off)
+    L = int(row_len)
+    ok = 0 < L < (1 << 31)  # else the call fails before it writes
+    out = np.zeros((max(n, 1), L) if ok else (1, 1), dtype=np.int32)[:n]  # never a NULL base
+    lengths = np.zeros(max(n, 1), dtype=np.int32)[:n] if with_lengths else None
+    mask = np.zeros((max(n, 1), L) if ok else (1, 1), dtype=np.uint8)[:n] if with_mask else None
+    stats = np.zeros(2, dtype=np.uint64) if with_stats else None
+    _check(lib().spm_hip_pad_ids_host(_p(ids), _p(off), n, row_len, pad_id, flags, _p(out),
+                                      _p(lengths) if with_lengths else None, _p(mask) if with_mask else None,
+                                      _p(stats) if with_stats else None))
+    return out, lengths, mask, stats
+
+
+def pack_ids_host(ids, off, row_len, pad_id, rows_capacity=None, with_seq=True, with_pos=True, with_stats=True,
+                  fill=0):
+    """spm_hip_pack_ids_host on a numpy id CSR (no GPU): (out, seq, pos, each
+    int32[rows_capacity, L], stats uint64[2]).  rows_capacity None: the rows
+    needed.  Rows the call leaves alone keep `fill`."""
+    ids, off, n = _host_csr(ids, off)
+    L = int(row_len)
+    ok = 0 < L < (1 << 31)
+    if rows_capacity is None:
+        rows_capacity = (int(off[-1]) - int(off[0]) + L - 1) // L if ok else 0
+    shape, rows = ((max(int(rows_capacity), 1), L), int(rows_capacity)) if ok else ((1, 1), 0)
+    out = np.full(shape, fill, dtype=np.int32)[:rows]  # never a NULL base
+    seq = np.full(shape, fill, dtype=np.int32)[:rows] if with_seq else None
+    pos = np.full(shape, fill, dtype=np.int32)[:rows] if with_pos else None
+    stats = np.zeros(2, dtype=np.uint64) if with_stats else None
+    _check(lib().spm_hip_pack_ids_host(_p(ids), _p(off), n, row_len, pad_id, rows_capacity, _p(out),
+                                       _p(seq) if with_seq else None, _p(pos) if with_pos else None,
+                                       _p(stats) if with_stats else None))
+    return out, seq, pos, stats
 
 
 class DeviceModel:
@@ -938,6 +1010,20 @@ class DeviceModel:
         id epilogue (spm_hip_finalize_ids) — SentencePieceProcessor::Encode(ids)
         per line.  Host lists in and out, torch for the device buffers."""
         import torch
+        d_out, d_ooff, k = self._lines_to_id_csr(lines, extra_options)
+        n = len(lines)
+        torch.cuda.synchronize(d_out.device)
+        out = d_out[:k].cpu().numpy()
+        oo = d_ooff.cpu().numpy()
+        return [out[int(oo[i]):int(oo[i + 1])].tolist() for i in range(n)]
+
+    def _lines_to_id_csr(self, lines, extra_options="", sample=None):
+        """The device chain of encode_lines_device up to the final id CSR:
+        (d_out int32, d_ooff int64[n+1], id count), torch tensors on the
+        current device, the work enqueued on the current stream.  sample =
+        (theta_or_alpha, seed, index_base): the sampler (BPE: BPE-dropout)
+        stands in for the encode."""
+        import torch
         dev = torch.device("cuda", torch.cuda.current_device())
         buf, off = to_csr(lines)
         n = len(lines)
@@ -955,8 +1041,13 @@ class DeviceModel:
         bf = self.byte_fallback() is not None
         d_len = torch.empty(max(tot.value, 1), dtype=torch.int32, device=dev) if bf else None
         d_tok = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        self.encode_device(d_norm.data_ptr(), d_noff.data_ptr(), n, d_ids.data_ptr(), d_tok.data_ptr(),
-                           d_len=d_len.data_ptr() if bf else None, stream=s)
+        if sample is None:
+            self.encode_device(d_norm.data_ptr(), d_noff.data_ptr(), n, d_ids.data_ptr(), d_tok.data_ptr(),
+                               d_len=d_len.data_ptr() if bf else None, stream=s)
+        else:
+            fn = self.bpe_dropout_encode_device if self.info().model_type == SPM_BPE else self.sample_encode_device
+            fn(d_norm.data_ptr(), d_noff.data_ptr(), n, sample[0], sample[1], d_ids.data_ptr(), d_tok.data_ptr(),
+               index_base=sample[2], d_len=d_len.data_ptr() if bf else None, stream=s)
         n_extra = sum(1 for o in extra_options.split(":") if o in ("bos", "eos"))
         ocap = tot.value + n * n_extra
         d_out = torch.empty(max(ocap, 1), dtype=torch.int32, device=dev)
@@ -968,10 +1059,46 @@ class DeviceModel:
             k = self.finalize_ids_bytes_device(extra_options, d_ids.data_ptr(), d_len.data_ptr(), d_tok.data_ptr(),
                                                n, d_norm.data_ptr(), d_noff.data_ptr(), d_out.data_ptr(), ocap,
                                                d_ooff.data_ptr(), stream=s)
-        torch.cuda.synchronize(dev)
-        out = d_out[:k].cpu().numpy()
-        oo = d_ooff.cpu().numpy()
-        return [out[int(oo[i]):int(oo[i + 1])].tolist() for i in range(n)]
+        return d_out, d_ooff, k
+
+    def encode_lines_padded(self, lines, row_len, pad_id, extra_options="", flags=0, sample=None):
+        """Raw lines -> (ids int32[n, L], lengths int32[n], mask bool[n, L]),
+        torch tensors on the current device: the chain of encode_lines_device,
+        then spm_hip_pad_ids on the current stream; no id visits the host.
+        flags: SPM_DENSE_PAD_LEFT | SPM_DENSE_TRUNCATE_LEFT | SPM_DENSE_KEEP_END.
+        sample = (theta_or_alpha, seed, index_base) runs SampleEncode (BPE:
+        BPE-dropout) in place of the encode."""
+        import torch
+        d_csr, d_ooff, _ = self._lines_to_id_csr(lines, extra_options, sample)
+        dev, n, L = d_csr.device, len(lines), int(row_len)
+        if not 0 < L < (1 << 31):
+            raise SpmError(SPM_INVALID_ARGUMENT, "row_len must be in [1, INT32_MAX]")
+        ids = torch.empty((n, L), dtype=torch.int32, device=dev)
+        lengths = torch.empty(n, dtype=torch.int32, device=dev)
+        mask = torch.empty((n, L), dtype=torch.uint8, device=dev)
+        if n == 0:  # empty tensors have no base to pass
+            return ids, lengths, mask.view(torch.bool)
+        pad_ids_device(d_csr.data_ptr(), d_ooff.data_ptr(), n, L, pad_id, flags, ids.data_ptr(), lengths.data_ptr(),
+                       mask.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        return ids, lengths, mask.view(torch.bool)
+
+    def encode_lines_packed(self, lines, row_len, pad_id, extra_options="", sample=None):
+        """Raw lines -> (ids, seq, pos), int32[ceil(T / L), L] torch tensors on
+        the current device: the lines' final ids as one stream of T slots
+        (spm_hip_pack_ids), seq the slot's line (-1 on padding), pos its
+        position in that line.  sample as in encode_lines_padded."""
+        import torch
+        d_csr, d_ooff, k = self._lines_to_id_csr(lines, extra_options, sample)
+        dev, n, L = d_csr.device, len(lines), int(row_len)
+        if not 0 < L < (1 << 31):
+            raise SpmError(SPM_INVALID_ARGUMENT, "row_len must be in [1, INT32_MAX]")
+        rows = (k + L - 1) // L  # the id count the epilogue returned
+        ids, seq, pos = (torch.empty((rows, L), dtype=torch.int32, device=dev) for _ in range(3))
+        if rows == 0:  # empty tensors have no base to pass
+            return ids, seq, pos
+        pack_ids_device(d_csr.data_ptr(), d_ooff.data_ptr(), n, L, pad_id, rows, ids.data_ptr(),
+                        seq.data_ptr(), pos.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        return ids, seq, pos
 
 
 class DevicePieces:
