@@ -521,6 +521,21 @@ void unigram_fast_kernel(FastArgs a) {
     constexpr int kMergeDepth = 5;
     constexpr bool kMerge = !kE;  // the E-step mode keeps its two-chain deep steps
     static_assert(kMergeDepth >= 5 && kMergeDepth + 2 < W, "merged inserts hold no node of length <= 4");
+    // Back-pointers leave once per group, not once per char start: p0 is a
+    // multiple of kU = 4, so ring slots 0..3 are the four bytes of Bw[0], and
+    // all four are final at the end of the group (a position's own slot after
+    // step q + 1 of its pair).  The backtrace reads back-pointers only at
+    // positions on the chain, which are char starts: what is stored for the
+    // other positions (position 0 included) is never read.  Inside the LDS
+    // window positions p0 .. p0 + 3 are the four bytes of one word of the
+    // lane, and the group stores Bw[0] as it is.  Past the window the scratch
+    // address bp + b0 + pos is not dword-aligned: those groups store their
+    // bytes one by one, up to position nb (the byte after it is the next
+    // sentence's), behind a branch that is the same for the whole group.  So
+    // the pairs hold no store and no test for one.  (The E-step mode keeps
+    // its byte store per char start, as it keeps its two-chain deep steps.)
+    constexpr bool kGroupBp = !kE;
+    static_assert(kLdsBpPos % kU == 0 && kU == 4, "a group lies on one side of the LDS window, in one word");
     uint32_t next_start = 0;
     for (uint32_t p0 = 0; p0 <= nb; p0 += kU) {
       StaticFor<0, kU / kNI>([&](auto pc) {
@@ -533,7 +548,9 @@ void unigram_fast_kernel(FastArgs a) {
           constexpr int q = decltype(qc)::value, j = jb + q;
           pp[q] = p0 + j;
           at[q] = pp[q] <= nb && pp[q] == next_start;
-          if (q == 0 && at[q] && pp[q] > 0) bp_store(pp[q], b_dist(std::integral_constant<int, j>{}));
+          if constexpr (!kGroupBp) {
+            if (q == 0 && at[q] && pp[q] > 0) bp_store(pp[q], b_dist(std::integral_constant<int, j>{}));
+          }
           st[q] = at[q] && pp[q] < nb;
           any[q] = (__builtin_amdgcn_ballot_w64(pp[q] == next_start) & __builtin_amdgcn_ballot_w64(pp[q] < nb)) != 0;
           cl[q] = OneCharLenDev(byte_of(std::integral_constant<int, j>{}));
@@ -685,7 +702,9 @@ void unigram_fast_kernel(FastArgs a) {
           StaticFor<0, kNI>([&](auto qc) {
             constexpr int q = decltype(qc)::value, j = jb + q, dd = d - 1 - q;
             if constexpr (dd == 1) {
-              if (q > 0 && at[q] && pp[q] > 0) bp_store(pp[q], b_dist(std::integral_constant<int, j>{}));
+              if constexpr (!kGroupBp) {
+                if (q > 0 && at[q] && pp[q] > 0) bp_store(pp[q], b_dist(std::integral_constant<int, j>{}));
+              }
               T0q[q] = T[j];
               Tbq[q] = TieBound(T0q[q], tie_mag);
               if constexpr (kE) {
@@ -770,6 +789,19 @@ void unigram_fast_kernel(FastArgs a) {
           }
         }
       });
+      // The group's four back-pointer bytes, final by now: one LDS word, or
+      // past the window the bytes of the positions up to nb.
+      if constexpr (kGroupBp) {
+        if (p0 < kLdsBpPos) {
+          lds_bp[(p0 >> 2) * kBlock + tid] = Bw[0];
+        } else {
+          StaticFor<0, kU>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (p0 + j <= nb)
+              __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(b_dist(jc)), bp_rsrc, lrel + p0 + j, 0, 0);
+          });
+        }
+      }
       // Next group: shift the ring and the byte window by kU.
 #pragma unroll
       for (int k = 0; k < kR; ++k) T[k] = k + kU < kR ? T[k + kU] : -__builtin_inff();

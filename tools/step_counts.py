@@ -3,6 +3,7 @@
 
   hipcc <the Makefile's HIPFLAGS> --cuda-device-only -S csrc/unigram_encode.hip -o k.s
   tools/step_counts.py k.s [kernel-symbol-substring]
+  tools/step_counts.py --prologue k.s [kernel-symbol-substring]   (see prologue())
 
 A walk step of the unigram byte kernel issues one pair of buffer_load_dwordx2
 (the two positions' (unit, score) gathers).  For every stretch of the kernel's
@@ -31,15 +32,85 @@ def kernel_body(lines, sub):
     return lines[start + 1:end]
 
 
+def count(seg):
+    return {"v_": sum(o.startswith("v_") for o in seg), "s_": sum(o.startswith("s_") for o in seg),
+            "branch": sum(o.startswith(("s_cbranch", "s_branch")) for o in seg),
+            "lds": sum(o.startswith("ds_") for o in seg),
+            "store": sum(o.startswith(("buffer_store", "global_store")) for o in seg)}
+
+
+def fmt(c):
+    return "v_ %3d  s_ %3d (branches %2d)  ds_ %d  stores %d" % (c["v_"], c["s_"], c["branch"], c["lds"], c["store"])
+
+
+def prologue(ops, sub):
+    """--prologue: the byte kernel's forward pass outside its walk steps.
+
+    pair prologue k: the stretch that ends at pair k's two root-table reads
+      (two adjacent ds_read_b64) and starts after the nearest unconditional
+      s_branch before them: char starts, the first position's back-pointer
+      store, the root reads' addresses (pair 0's stretch begins with the
+      loop's latch).
+    back-pointer store: every byte store of the forward loop with its guard,
+      from the s_and_saveexec that opens it to the s_or_b64 exec that closes it.
+    group epilogue: the stretch between two unconditional branches that holds
+      the loop's window load (the first buffer_load_dword after the last root
+      read): back-pointer word store, ring shift, window advance."""
+    roots = [n for n in range(len(ops) - 1) if ops[n] == "ds_read_b64" and ops[n + 1] == "ds_read_b64"]
+    if not roots:
+        sys.exit("no root-table reads (not a byte-kernel instantiation)")
+    print("# %s: %d instructions, %d pair prologues" % (sub, len(ops), len(roots)))
+
+    def back_to_branch(n):
+        while n > 0 and ops[n - 1] != "s_branch":
+            n -= 1
+        return n
+
+    for k, r in enumerate(roots):
+        print("pair prologue %d        %s" % (k, fmt(count(ops[back_to_branch(r):r]))))
+    win = next(n for n in range(roots[-1], len(ops)) if ops[n] == "buffer_load_dword")
+    stores = [n for n in range(roots[0] - 80, win) if ops[n] in ("ds_write_b8", "ds_write_b8_d16_hi", "buffer_store_byte")]
+    # A site: the stores at most 12 instructions apart (the scratch and the LDS side of one guarded store).
+    groups = []
+    for n in stores:
+        if groups and n - groups[-1][-1] <= 12:
+            groups[-1].append(n)
+        else:
+            groups.append([n])
+    sites = []
+    for g in groups:
+        a, b = g[0], g[-1]
+        while a > 0 and not ops[a].startswith("s_and_saveexec"):
+            a -= 1
+        while b + 1 < len(ops) and ops[b] != "s_or_b64":
+            b += 1
+        sites.append((a, b))
+    for k, (a, b) in enumerate(sites):
+        print("back-pointer store %d   %s" % (k, fmt(count(ops[a:b + 1]))))
+    if not sites:
+        print("back-pointer store     none in the forward loop")
+    e0 = back_to_branch(win)
+    e1 = next(n for n in range(win, len(ops)) if ops[n] == "s_branch")
+    seg = ops[e0:e1 + 1]
+    c = count(seg)
+    # (The word store's block may be laid out behind the stretch's closing branch.)
+    print("group epilogue         %s  (v_mov %d; ds_write_b32 in it or in the 60 instructions behind it: %d)" % (
+        fmt(c), sum(o.startswith("v_mov") for o in seg), sum(o == "ds_write_b32" for o in ops[e0:e1 + 61])))
+
+
 def main():
-    path = sys.argv[1]
-    sub = sys.argv[2] if len(sys.argv) > 2 else DEFAULT
+    argv = [x for x in sys.argv[1:] if x != "--prologue"]
+    path = argv[0]
+    sub = argv[1] if len(argv) > 1 else DEFAULT
     body = kernel_body(open(path).read().split("\n"), sub)
     ops = []
     for ln in body:
         m = re.match(r"\s+([a-z_0-9]+)", ln)
         if m and not ln.lstrip().startswith((".", ";")):
             ops.append(m.group(1))
+    if "--prologue" in sys.argv[1:]:
+        prologue(ops, sub)
+        return
     loads = [n for n, o in enumerate(ops) if o == "buffer_load_dwordx2"]
     # A pair: two gathers at most 8 instructions apart.
     pairs, n = [], 0
