@@ -1065,8 +1065,36 @@ int spm_hip_count_ids_host(spm_hip_model *model, const int32_t *ids, uint64_t nu
  * needed = ceil(T / L), T).  Rows beyond rows_capacity are not written and
  * rows between ceil(T / L) and rows_capacity are not touched, so a caller who
  * sized by d_stats[0], or by the total spm_hip_finalize_ids returns, gets
- * exactly its rows.  Packing whole sentences into rows without splitting them
- * (bin packing) is out of scope.
+ * exactly its rows.
+ *
+ * Fit: whole sentences share a row and none is split (in-order next-fit).
+ * k_i = min(len_i, L).  With (row, used) = (0, 0), the sentences in order: an
+ * empty one is skipped and occupies nothing; else, if used + k_i > L, the next
+ * row is opened (++row, used = 0); the sentence takes columns
+ * [used, used + k_i) of row and used += k_i.  A sentence longer than L is cut
+ * as in pad, over its own k_i columns: SPM_DENSE_TRUNCATE_LEFT and
+ * SPM_DENSE_KEEP_END mean what they mean there, SPM_DENSE_PAD_LEFT is
+ * SPM_INVALID_ARGUMENT.  Every other slot of rows [0, R) holds pad_id; R is
+ * row + 1 if a token was placed, else 0.  Outputs: d_out[rows_capacity*L];
+ * nullable d_seq (int32 per slot: the sentence, -1 on padding), d_pos (int32
+ * per slot: the kept-slot index j in [0, k_i), the position id of a
+ * packed-attention batch, contiguous in every sentence, a cut one included; 0
+ * on padding), d_row_lengths[rows_capacity] (int32: the used slots of a row),
+ * d_place[n] (uint64: row * L + first column of sentence i, UINT64_MAX for an
+ * empty one) and d_stats[4] (uint64: rows needed R, tokens placed, sentences
+ * cut, tokens dropped).  Rows at or past rows_capacity are not written, rows in
+ * [R, rows_capacity) are not touched; d_stats is always complete and d_place
+ * is written for every sentence, those whose row was not written included.
+ * Sizing: two consecutive rows together hold more than L tokens, so
+ * R <= max(0, 2 * ceil(K / L) - 1) with K = sum k_i <= T, and R <= the number
+ * of non-empty sentences.  The call works in d_scratch (device memory, 16-byte
+ * aligned, contents undefined before and after), scratch_bytes of it, at least
+ * what spm_hip_fit_ids_scratch_bytes(n, row_len, rows_capacity) returns (host
+ * only; 0 for n == 0, when d_scratch may be null); too little is
+ * SPM_INVALID_ARGUMENT, as is n > INT32_MAX.  d_stats = {0, 0, 0, 0} for
+ * n == 0.  spm_hip_fit_ids_host takes no scratch.  (Both device entries read
+ * the test knob SPM_HIP_FIT_GEOMETRY from the environment at every call; it
+ * changes the scratch size, so it must not change between the two.)
  *
  * The device calls are pure stream calls in the sense of the _async entries:
  * they allocate nothing, do not synchronize and read nothing back, and every
@@ -1093,6 +1121,14 @@ int spm_hip_pad_ids_host(const int32_t *ids, const uint64_t *offsets, uint64_t n
 int spm_hip_pack_ids_host(const int32_t *ids, const uint64_t *offsets, uint64_t n, uint32_t row_len,
                           int32_t pad_id, uint64_t rows_capacity, int32_t *out, int32_t *seq, int32_t *pos,
                           uint64_t *stats);
+int spm_hip_fit_ids(const int32_t *d_ids, const uint64_t *d_offsets, uint64_t n, uint32_t row_len,
+                    int32_t pad_id, uint32_t flags, uint64_t rows_capacity, int32_t *d_out, int32_t *d_seq,
+                    int32_t *d_pos, int32_t *d_row_lengths, uint64_t *d_place, uint64_t *d_stats, void *d_scratch,
+                    uint64_t scratch_bytes, void *stream);
+int spm_hip_fit_ids_scratch_bytes(uint64_t n, uint32_t row_len, uint64_t rows_capacity, uint64_t *bytes);
+int spm_hip_fit_ids_host(const int32_t *ids, const uint64_t *offsets, uint64_t n, uint32_t row_len,
+                         int32_t pad_id, uint32_t flags, uint64_t rows_capacity, int32_t *out, int32_t *seq,
+                         int32_t *pos, int32_t *row_lengths, uint64_t *place, uint64_t *stats);
 
 /* Device memory this library holds in the calling process (every block it
  * allocates: models' workspaces, E-step piece sets, trainer corpus and

@@ -33,15 +33,6 @@
 namespace spm_amd {
 namespace {
 
-__device__ __forceinline__ void StoreQuad(int32_t *__restrict__ p, uint64_t t, const int32_t v[4], uint32_t cnt,
-                                          bool vec) {
-  if (vec && cnt == 4) {
-    *reinterpret_cast<int4 *>(p + t) = make_int4(v[0], v[1], v[2], v[3]);
-  } else {
-    for (uint32_t j = 0; j < cnt; ++j) p[t + j] = v[j];
-  }
-}
-
 __global__ __launch_bounds__(256) void dense_pad_kernel(const int32_t *__restrict__ ids,
                                                         const uint64_t *__restrict__ off, uint64_t n, uint32_t L,
                                                         int32_t pad_id, uint32_t flags, int32_t *__restrict__ out,

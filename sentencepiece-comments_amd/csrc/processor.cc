@@ -380,7 +380,7 @@ Status SentencePieceProcessor::SampleEncode(const std::string &input, int nbest_
 namespace {
 enum {
   kIn, kInOff, kNorm, kNormOff, kIds, kLen, kTok, kOut, kOutOff, kSmallBlockSlot, kCounts,
-  kDenseIds, kDenseAux0, kDenseAux1, kDenseStats
+  kDenseIds, kDenseAux0, kDenseAux1, kDenseStats, kDenseScratch, kDenseRowLengths, kDensePlace
 };
 }  // namespace
 
@@ -689,7 +689,10 @@ Status SentencePieceProcessor::RunDense(const std::vector<std::string> &inputs, 
   if (host_only_) return Err(SPM_FAILED_PRECONDITION, "host-only processor");
   if (!out) return Err(SPM_INTERNAL, "output container is null");
   if (o.row_len == 0 || o.row_len > 0x7FFFFFFFu) return Err(SPM_INVALID_ARGUMENT, "row_len must be in [1, INT32_MAX]");
-  if (o.flags & ~(o.pack ? 0u : SPM_DENSE_PAD_LEFT | SPM_DENSE_TRUNCATE_LEFT | SPM_DENSE_KEEP_END))
+  const bool whole = o.pack && o.whole;
+  if (o.flags & ~(whole    ? SPM_DENSE_TRUNCATE_LEFT | SPM_DENSE_KEEP_END
+                  : o.pack ? 0u
+                           : SPM_DENSE_PAD_LEFT | SPM_DENSE_TRUNCATE_LEFT | SPM_DENSE_KEEP_END))
     return Err(SPM_INVALID_ARGUMENT, "unknown dense flag bit");
   *out = DenseBatch();
   out->row_len = o.row_len;
@@ -727,14 +730,48 @@ Status SentencePieceProcessor::RunDense(const std::vector<std::string> &inputs, 
     if (!st.ok()) return st;
   }
   // Pack: the row count comes from the id count the epilogue returned.
-  const uint64_t rows = o.pack ? (fin + L - 1) / L : n;
+  // Whole: the bound of spm_hip_fit_ids; the rows needed are read back below.
+  uint64_t rows = o.pack ? (fin + L - 1) / L : n;
+  if (whole) rows = std::min<uint64_t>(n, rows ? 2 * rows - 1 : 0);
   if (rows > std::numeric_limits<uint64_t>::max() / (4 * L)) return Err(SPM_OUT_OF_RANGE, "rows * row_len is too large");
-  const uint64_t slots = rows * L;
+  uint64_t slots = rows * L;
   int32_t *d_ids = static_cast<int32_t *>(dev_.Get(kDenseIds, slots * 4));
   void *d_a0 = dev_.Get(kDenseAux0, o.pack ? slots * 4 : n * 4);  // seq | lengths
   void *d_a1 = dev_.Get(kDenseAux1, o.pack ? slots * 4 : slots);  // pos | mask
-  uint64_t *d_stats = static_cast<uint64_t *>(dev_.Get(kDenseStats, 16));
+  uint64_t *d_stats = static_cast<uint64_t *>(dev_.Get(kDenseStats, 32));
   if (!d_ids || !d_a0 || !d_a1 || !d_stats) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+  if (whole) {
+    uint64_t scratch_bytes = 0;
+    Status ws = FromC(spm_hip_fit_ids_scratch_bytes(n, o.row_len, rows, &scratch_bytes));
+    if (!ws.ok()) return ws;
+    void *d_scratch = dev_.Get(kDenseScratch, scratch_bytes);
+    int32_t *d_rl = static_cast<int32_t *>(dev_.Get(kDenseRowLengths, rows * 4));
+    uint64_t *d_place = static_cast<uint64_t *>(dev_.Get(kDensePlace, n * 8));
+    if (!d_scratch || !d_rl || !d_place) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+    ws = FromC(spm_hip_fit_ids(d_csr, d_csr_off, n, o.row_len, o.pad_id, o.flags, rows, d_ids,
+                               static_cast<int32_t *>(d_a0), static_cast<int32_t *>(d_a1), d_rl, d_place, d_stats,
+                               d_scratch, scratch_bytes, nullptr));
+    if (!ws.ok()) return ws;
+    uint64_t stats[4] = {0, 0, 0, 0};
+    if ((he = hipMemcpy(stats, d_stats, 32, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(he);
+    out->ids = d_ids;
+    out->seq = static_cast<const int32_t *>(d_a0);
+    out->pos = static_cast<const int32_t *>(d_a1);
+    out->row_lengths = d_rl;
+    out->place = d_place;
+    out->stats = d_stats;
+    out->rows = stats[0];
+    out->tokens = fin;
+    out->cut = stats[2];
+    out->dropped = stats[3];
+    if (host_ids) {
+      slots = stats[0] * L;
+      host_ids->resize(slots);
+      if (slots && (he = hipMemcpy(host_ids->data(), d_ids, slots * 4, hipMemcpyDeviceToHost)) != hipSuccess)
+        return fail_hip(he);
+    }
+    return Status::Ok();
+  }
   Status st = FromC(o.pack ? spm_hip_pack_ids(d_csr, d_csr_off, n, o.row_len, o.pad_id, rows, d_ids,
                                               static_cast<int32_t *>(d_a0), static_cast<int32_t *>(d_a1), d_stats,
                                               nullptr)

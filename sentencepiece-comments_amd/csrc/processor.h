@@ -146,13 +146,16 @@ class SentencePieceProcessor {
   // the same GPU.  pack = false: one line per row, padded with pad_id or cut
   // to row_len (flags: SPM_DENSE_PAD_LEFT, SPM_DENSE_TRUNCATE_LEFT,
   // SPM_DENSE_KEEP_END).  pack = true: the lines' ids run on as one stream of
-  // row_len slots per row (flags must be 0).  The extra options are part of
-  // the ids, so they apply before padding.
+  // row_len slots per row (flags must be 0).  pack and whole: whole lines share
+  // a row and none is split (spm_hip_fit_ids; flags: SPM_DENSE_TRUNCATE_LEFT,
+  // SPM_DENSE_KEEP_END for a line longer than a row).  The extra options are
+  // part of the ids, so they apply before padding.
   struct DenseOptions {
     uint32_t row_len = 0;
     int32_t pad_id = 0;
     uint32_t flags = 0;
     bool pack = false;
+    bool whole = false;  // meaningful with pack
   };
   // Device pointers, owned by the processor and valid until the next call on
   // the instance; the work that fills them is enqueued on the null stream.
@@ -162,12 +165,16 @@ class SentencePieceProcessor {
     const uint8_t *mask = nullptr;     // pad: [rows, row_len], 1 on token slots
     const int32_t *seq = nullptr;      // pack: [rows, row_len], the slot's line, -1 on padding
     const int32_t *pos = nullptr;      // pack: [rows, row_len], the slot's position in its line
-    const uint64_t *stats = nullptr;   // pad: {lines cut, tokens dropped}; pack: {rows, tokens}
-    uint64_t rows = 0;                 // pad: the lines; pack: ceil(tokens / row_len)
+    const uint64_t *stats = nullptr;   // pad: {lines cut, tokens dropped}; pack: {rows, tokens};
+                                       // whole: {rows, tokens placed, lines cut, tokens dropped}
+    uint64_t rows = 0;                 // pad: the lines; pack: ceil(tokens / row_len); whole: the rows
+                                       // needed (the call waits for the device to read them)
     uint32_t row_len = 0;
     uint64_t tokens = 0;  // final ids of the batch before padding
-    // Only with host_ids (the call then waits for the device): the stats of pad.
+    // Only with host_ids (the call then waits for the device): the stats of pad; always with whole.
     uint64_t cut = 0, dropped = 0;
+    const int32_t *row_lengths = nullptr;  // whole: [rows], the used slots of a row
+    const uint64_t *place = nullptr;       // whole: [lines], row * row_len + first column, UINT64_MAX if empty
   };
   // Nothing but the id count comes back to the host unless host_ids is given
   // (then it receives the rows * row_len ids).  A WORD or CHAR model takes its
@@ -297,8 +304,8 @@ class SentencePieceProcessor {
                       uint64_t count, std::vector<std::pair<std::string, int>> *out) const;
   // Grow-only device staging for EncodeBatch (raw lines → normalized → ids).
   struct Staging {
-    void *ptr[15] = {};
-    size_t cap[15] = {};
+    void *ptr[18] = {};
+    size_t cap[18] = {};
     void *Get(int k, size_t bytes);
     ~Staging();
   };

@@ -3868,6 +3868,27 @@ int PackArgs(const uint64_t *off, uint64_t n, uint32_t row_len, const int32_t *o
   return SPM_OK;
 }
 
+int FitArgs(const uint64_t *off, uint64_t n, uint32_t row_len, uint32_t flags, const int32_t *out,
+            uint64_t *rows_capacity) {
+  const int rc = DenseArgs(off, row_len, flags, out);
+  if (rc != SPM_OK) return rc;
+  if (flags & SPM_DENSE_PAD_LEFT) return Fail(SPM_INVALID_ARGUMENT, "SPM_DENSE_PAD_LEFT has no meaning for fit");
+  if (n > 0x7FFFFFFFull) return Fail(SPM_INVALID_ARGUMENT, "too many sentences in one batch");
+  *rows_capacity = std::min(*rows_capacity, std::numeric_limits<uint64_t>::max() / row_len);
+  return SPM_OK;
+}
+
+// Test knob SPM_HIP_FIT_GEOMETRY="branch,top_walk": small values take a small
+// batch through every level of the composition (dense.h).
+spm_amd::FitGeometry FitGeometryNow() {
+  spm_amd::FitGeometry g{spm_amd::kFitBranch, spm_amd::kFitTopWalk};
+  if (const char *e = std::getenv("SPM_HIP_FIT_GEOMETRY")) {
+    unsigned b = 0, w = 0;
+    if (std::sscanf(e, "%u,%u", &b, &w) == 2 && b >= 2 && b <= 1024 && w >= 1 && w <= 65536) g = {b, w};
+  }
+  return g;
+}
+
 }  // namespace
 
 int spm_hip_pad_ids(const int32_t *d_ids, const uint64_t *d_off, uint64_t n, uint32_t row_len, int32_t pad_id,
@@ -3908,6 +3929,45 @@ int spm_hip_pack_ids_host(const int32_t *ids, const uint64_t *off, uint64_t n, u
   const int rc = PackArgs(off, n, row_len, out, &rows_capacity);
   if (rc != SPM_OK) return rc;
   spm_amd::DensePackHostLoop(ids, off, n, row_len, pad_id, rows_capacity, out, seq, pos, stats);
+  return SPM_OK;
+}
+
+int spm_hip_fit_ids_scratch_bytes(uint64_t n, uint32_t row_len, uint64_t rows_capacity, uint64_t *bytes) {
+  if (!bytes) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (row_len == 0 || row_len > 0x7FFFFFFFu) return Fail(SPM_INVALID_ARGUMENT, "row_len must be in [1, INT32_MAX]");
+  if (n > 0x7FFFFFFFull) return Fail(SPM_INVALID_ARGUMENT, "too many sentences in one batch");
+  *bytes = n ? spm_amd::FitPlanFor(n, rows_capacity, FitGeometryNow()).bytes : 0;
+  return SPM_OK;
+}
+
+int spm_hip_fit_ids(const int32_t *d_ids, const uint64_t *d_off, uint64_t n, uint32_t row_len, int32_t pad_id,
+                    uint32_t flags, uint64_t rows_capacity, int32_t *d_out, int32_t *d_seq, int32_t *d_pos,
+                    int32_t *d_row_lengths, uint64_t *d_place, uint64_t *d_stats, void *d_scratch,
+                    uint64_t scratch_bytes, void *stream) {
+  const int rc = FitArgs(d_off, n, row_len, flags, d_out, &rows_capacity);
+  if (rc != SPM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (n == 0) {
+    SPM_HIP_TRY(spm_amd::LaunchDenseFitEmpty(d_stats, st));
+    return SPM_OK;
+  }
+  const spm_amd::FitGeometry g = FitGeometryNow();
+  const spm_amd::FitPlan plan = spm_amd::FitPlanFor(n, rows_capacity, g);
+  if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15) || scratch_bytes < plan.bytes)
+    return Fail(SPM_INVALID_ARGUMENT, "scratch is null, not 16-byte aligned or smaller than spm_hip_fit_ids_scratch_bytes");
+  spm_amd::TraceRange trace_range_("spm_hip_fit_ids");
+  SPM_HIP_TRY(spm_amd::LaunchDenseFit(d_ids, d_off, n, row_len, pad_id, flags, rows_capacity, d_out, d_seq, d_pos,
+                                      d_row_lengths, d_place, d_stats, d_scratch, plan, g, st));
+  return SPM_OK;
+}
+
+int spm_hip_fit_ids_host(const int32_t *ids, const uint64_t *off, uint64_t n, uint32_t row_len, int32_t pad_id,
+                         uint32_t flags, uint64_t rows_capacity, int32_t *out, int32_t *seq, int32_t *pos,
+                         int32_t *row_lengths, uint64_t *place, uint64_t *stats) {
+  const int rc = FitArgs(off, n, row_len, flags, out, &rows_capacity);
+  if (rc != SPM_OK) return rc;
+  spm_amd::DenseFitHostLoop(ids, off, n, row_len, pad_id, flags, rows_capacity, out, seq, pos, row_lengths, place,
+                            stats);
   return SPM_OK;
 }
 

@@ -58,11 +58,15 @@ EXPORTED = [
     "spm_hip_model_reset_vocabulary", "spm_hip_count_ids", "spm_hip_count_ids_host",
     "spm_hip_model_byte_fallback", "spm_hip_finalize_ids_bytes", "spm_hip_finalize_ids_bytes_async",
     "spm_hip_pad_ids", "spm_hip_pack_ids", "spm_hip_pad_ids_host", "spm_hip_pack_ids_host",
+    "spm_hip_fit_ids", "spm_hip_fit_ids_scratch_bytes", "spm_hip_fit_ids_host",
 ]
 # Flags of spm_hip_pad_ids (include/spm_hip.h).
 SPM_DENSE_PAD_LEFT, SPM_DENSE_TRUNCATE_LEFT, SPM_DENSE_KEEP_END = 1, 2, 4
 # Dense kernels (csrc/dense.h): blocks of a pad / pack launch and slots a block covers per step.
 DENSE_BLOCKS, DENSE_PACK_BLOCKS, DENSE_TILE_SLOTS = 1024, 2048, 1024
+# Fit (csrc/dense.h): sentences of a level-0 tile, tiles of a level per tile of the next, tiles one thread
+# walks at the top, chunks of the prefix scan.  SPM_HIP_FIT_GEOMETRY="branch,top_walk" is the test knob.
+FIT_TILE, FIT_BRANCH, FIT_TOP_WALK, FIT_SCAN_TILES = 4096, 16, 256, 1024
 
 ABI_VERSION = 3  # SPM_HIP_ABI_VERSION of include/spm_hip.h (struct layouts below)
 
@@ -270,6 +274,9 @@ def lib():
         L.spm_hip_pack_ids.argtypes = [P, P, U64, U32, I32, U64, P, P, P, P, P]
         L.spm_hip_pad_ids_host.argtypes = [P, P, U64, U32, I32, U32, P, P, P, P]
         L.spm_hip_pack_ids_host.argtypes = [P, P, U64, U32, I32, U64, P, P, P, P]
+        L.spm_hip_fit_ids.argtypes = [P, P, U64, U32, I32, U32, U64, P, P, P, P, P, P, P, U64, P]
+        L.spm_hip_fit_ids_scratch_bytes.argtypes = [U64, U32, U64, P]
+        L.spm_hip_fit_ids_host.argtypes = [P, P, U64, U32, I32, U32, U64, P, P, P, P, P, P]
         _lib = L
     return _lib
 
@@ -337,6 +344,26 @@ def pack_ids_device(d_ids, d_off, n, row_len, pad_id, rows_capacity, d_out, d_se
                                   _vp(d_pos), _vp(d_stats), _vp(stream)))
 
 
+def fit_ids_scratch_bytes(n, row_len, rows_capacity):
+    """spm_hip_fit_ids_scratch_bytes: the device scratch one spm_hip_fit_ids call needs (host only)."""
+    b = ctypes.c_uint64()
+    _check(lib().spm_hip_fit_ids_scratch_bytes(n, row_len, rows_capacity, ctypes.byref(b)))
+    return b.value
+
+
+def fit_rows_bound(tokens, n, row_len):
+    """Rows spm_hip_fit_ids can need for n sentences of `tokens` ids in all."""
+    return min(n, max(0, 2 * ((tokens + row_len - 1) // row_len) - 1))
+
+
+def fit_ids_device(d_ids, d_off, n, row_len, pad_id, flags, rows_capacity, d_out, d_scratch, scratch_bytes,
+                   d_seq=None, d_pos=None, d_row_lengths=None, d_place=None, d_stats=None, stream=None):
+    """spm_hip_fit_ids on device pointers (ints): a pure stream call, no model handle."""
+    _check(lib().spm_hip_fit_ids(_vp(d_ids), _vp(d_off), n, row_len, pad_id, flags, rows_capacity, _vp(d_out),
+                                 _vp(d_seq), _vp(d_pos), _vp(d_row_lengths), _vp(d_place), _vp(d_stats),
+                                 _vp(d_scratch), scratch_bytes, _vp(stream)))
+
+
 def _host_csr(ids, off):
     ids = np.ascontiguousarray(ids, dtype=np.int32)
     off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -379,6 +406,26 @@ def pack_ids_host(ids, off, row_len, pad_id, rows_capacity=None, with_seq=True, 
                                        _p(seq) if with_seq else None, _p(pos) if with_pos else None,
                                        _p(stats) if with_stats else None))
     return out, seq, pos, stats
+
+
+def fit_ids_host(ids, off, row_len, pad_id, flags=0, rows_capacity=None, fill=0):
+    """spm_hip_fit_ids_host on a numpy id CSR (no GPU): (out, seq, pos, each
+    int32[rows_capacity, L], row_lengths int32[rows_capacity], place uint64[n],
+    stats uint64[4]).  rows_capacity None: fit_rows_bound.  What the call
+    leaves alone keeps `fill`."""
+    ids, off, n = _host_csr(ids, off)
+    L = int(row_len)
+    ok = 0 < L < (1 << 31)
+    if rows_capacity is None:
+        rows_capacity = fit_rows_bound(int(off[-1]) - int(off[0]), n, L) if ok else 0
+    shape, rows = ((max(int(rows_capacity), 1), L), int(rows_capacity)) if ok else ((1, 1), 0)
+    out, seq, pos = (np.full(shape, fill, dtype=np.int32)[:rows] for _ in range(3))  # never a NULL base
+    row_lengths = np.full(shape[0], fill, dtype=np.int32)[:rows]
+    place = np.zeros(max(n, 1), dtype=np.uint64)[:n]
+    stats = np.zeros(4, dtype=np.uint64)
+    _check(lib().spm_hip_fit_ids_host(_p(ids), _p(off), n, row_len, pad_id, flags, rows_capacity, _p(out), _p(seq),
+                                      _p(pos), _p(row_lengths), _p(place), _p(stats)))
+    return out, seq, pos, row_lengths, place, stats
 
 
 class DeviceModel:
@@ -1099,6 +1146,34 @@ class DeviceModel:
         pack_ids_device(d_csr.data_ptr(), d_ooff.data_ptr(), n, L, pad_id, rows, ids.data_ptr(),
                         seq.data_ptr(), pos.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
         return ids, seq, pos
+
+    def encode_lines_fitted(self, lines, row_len, pad_id, extra_options="", flags=0, sample=None):
+        """Raw lines -> (ids, seq, pos int32[R, L], row_lengths int32[R]) torch
+        tensors on the current device: whole lines share a row and none is
+        split (spm_hip_fit_ids).  seq is the slot's line (-1 on padding), pos
+        its position among the line's kept ids.  The buffers are sized by the
+        bound on the rows; the rows needed are read back (the one
+        synchronization) and the first R rows returned.  flags:
+        SPM_DENSE_TRUNCATE_LEFT | SPM_DENSE_KEEP_END; sample as in
+        encode_lines_padded."""
+        import torch
+        d_csr, d_ooff, k = self._lines_to_id_csr(lines, extra_options, sample)
+        dev, n, L = d_csr.device, len(lines), int(row_len)
+        if not 0 < L < (1 << 31):
+            raise SpmError(SPM_INVALID_ARGUMENT, "row_len must be in [1, INT32_MAX]")
+        cap = fit_rows_bound(k, n, L)
+        ids, seq, pos = (torch.empty((cap, L), dtype=torch.int32, device=dev) for _ in range(3))
+        row_lengths = torch.empty(cap, dtype=torch.int32, device=dev)
+        if cap == 0:  # empty tensors have no base to pass
+            return ids, seq, pos, row_lengths
+        nbytes = fit_ids_scratch_bytes(n, L, cap)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        stats = torch.empty(4, dtype=torch.int64, device=dev)
+        fit_ids_device(d_csr.data_ptr(), d_ooff.data_ptr(), n, L, pad_id, flags, cap, ids.data_ptr(),
+                       scratch.data_ptr(), nbytes, seq.data_ptr(), pos.data_ptr(), row_lengths.data_ptr(), None,
+                       stats.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        rows = int(stats[0].item())
+        return ids[:rows], seq[:rows], pos[:rows], row_lengths[:rows]
 
 
 class DevicePieces:

@@ -11,7 +11,10 @@ Id batches, each encoded on the device first:
             likewise
 Workloads: pad of c2 at L = 16, pad of botchan and wagahaiwa at L = 64 and
 L = 512 (all outputs: ids, lengths, mask, stats), pack of c2 and botchan at
-L = 2048 (ids, seq, pos, stats).  Per workload, in one run:
+L = 2048 (ids, seq, pos, stats); fit (spm_hip_fit_ids, all outputs) of c2 at
+L = 16 and L = 2048 and of botchan and wagahaiwa at L = 512, timed in pairs
+with spm_hip_pack_ids on the same ids (--fit-only skips the rest).  Per
+workload, in one run:
 
   * the kernel's time (HIP events around the stream call) and a restatement of
     the same result with torch ops on the same CSR on the device, warmed up and
@@ -45,6 +48,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fit-only", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -55,7 +59,7 @@ def main():
         sys.exit("dense_bench: no GPU; nothing measured")
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    lines = []
+    lines = ["python tools/dense_bench.py " + " ".join(sys.argv[1:])]
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -158,6 +162,52 @@ def main():
         lines.append("%s: pack, %d sentences, %d ids, L = %d, %d rows" % (name, n, T, L, rows))
         report(name, moved, times, same)
 
+    def fit(name, d_ids, d_off, L, pad_id=-1):
+        """spm_hip_fit_ids beside spm_hip_pack_ids on the same ids, and the one-thread host loop once."""
+        import time
+        n = d_off.numel() - 1
+        T = int((d_off[-1] - d_off[0]).item())
+        cap = spm_amd.fit_rows_bound(T, n, L)
+        prow = (T + L - 1) // L
+        out, seq, pos = (torch.empty((cap, L), dtype=torch.int32, device=dev) for _ in range(3))
+        rl = torch.empty(cap, dtype=torch.int32, device=dev)
+        place = torch.empty(n, dtype=torch.int64, device=dev)
+        stats = torch.empty(4, dtype=torch.int64, device=dev)
+        nbytes = spm_amd.fit_ids_scratch_bytes(n, L, cap)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+        def kernel():
+            spm_amd.fit_ids_device(d_ids.data_ptr(), d_off.data_ptr(), n, L, pad_id, 0, cap, out.data_ptr(),
+                                   scratch.data_ptr(), nbytes, seq.data_ptr(), pos.data_ptr(), rl.data_ptr(),
+                                   place.data_ptr(), stats.data_ptr(), stream=stream)
+
+        def packed():
+            spm_amd.pack_ids_device(d_ids.data_ptr(), d_off.data_ptr(), n, L, pad_id, prow, out.data_ptr(),
+                                    seq.data_ptr(), pos.data_ptr(), stream=stream)
+
+        times, _, _ = pairs(packed, kernel)
+        kernel()
+        torch.cuda.synchronize(dev)
+        R, kept = int(stats[0].item()), int(stats[1].item())
+        t0 = time.perf_counter()
+        h = spm_amd.fit_ids_host(d_ids.cpu().numpy(), d_off.cpu().numpy().view(np.uint64), L, pad_id, 0,
+                                 rows_capacity=R)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        same = all(np.array_equal(a[:R].cpu().numpy(), b) for a, b in zip((out, seq, pos, rl), h[:4]))
+        same = same and np.array_equal(place.cpu().numpy().view(np.uint64), h[4]) and stats.tolist() == h[5].tolist()
+        moved = 8 * (n + 1) + 4 * kept + 3 * 4 * R * L + 4 * R + 8 * n + 32
+        lines.append("%s: fit, %d sentences, %d ids, L = %d, %d rows (pack: %d), %d bytes of scratch; pack on the same "
+                     "ids median %.3f ms (min %.3f, max %.3f); fit / pack = %.2f; one-thread host loop (with its "
+                     "buffers) %.1f ms; equal to the host loop: %s"
+                     % (name, n, T, L, R, prow, nbytes, times[0][0], times[0][1], times[0][2],
+                        times[1][0] / times[0][0], host_ms, same))
+        src, dst = (torch.empty(moved, dtype=torch.uint8, device=dev) for _ in range(2))
+        c = [timed(lambda: dst.copy_(src))[0] for _ in range(args.warmup + args.pairs)][args.warmup:]
+        k = times[1]
+        lines.append("%s  kernels (stream call, HIP events) median %.3f ms (min %.3f, max %.3f): %d bytes needed, "
+                     "%.1f GB/s; device-to-device copy of that many bytes median %.3f ms"
+                     % (name, k[0], k[1], k[2], moved, moved / (k[0] * 1e-3) / 1e9, statistics.median(c)))
+
     # c2: the synthetic batch, encoded on the device (model-level ids are final ids here: no extra options).
     buf, off = synth.normalized(args.sentences, seed=1234)
     dm = spm_amd.DeviceModel(open(os.path.join(ROOT, "data", "synth32k_unigram.model"), "rb").read())
@@ -170,8 +220,11 @@ def main():
     torch.cuda.synchronize(dev)
     c2_ids = c2_ids[:int(c2_off[-1].item())].clone()
     del d_bytes, d_boff, dm
-    pad("c2 L=16", c2_ids, c2_off, 16)
-    pack("c2 L=2048", c2_ids, c2_off, 2048)
+    if not args.fit_only:
+        pad("c2 L=16", c2_ids, c2_off, 16)
+        pack("c2 L=2048", c2_ids, c2_off, 2048)
+    fit("c2 L=16", c2_ids, c2_off, 16)
+    fit("c2 L=2048", c2_ids, c2_off, 2048)
     del c2_ids, c2_off
 
     gold = os.path.join(ROOT, "tests", "golden")
@@ -188,10 +241,11 @@ def main():
         d_ids = d_fin[:k].repeat(reps)
         d_off = torch.from_numpy(toff).to(dev)
         del dm, d_fin, d_foff
-        for L in (64, 512):
+        for L in () if args.fit_only else (64, 512):
             pad("%s x%d L=%d" % (name, reps, L), d_ids, d_off, L)
-        if name == "botchan":
+        if name == "botchan" and not args.fit_only:
             pack("%s x%d L=2048" % (name, reps), d_ids, d_off, 2048)
+        fit("%s x%d L=512" % (name, reps), d_ids, d_off, 512)
         del d_ids, d_off
         torch.cuda.empty_cache()
 
