@@ -446,6 +446,25 @@ int spm_hip_model_set_nbest_max_hyps(spm_hip_model *model, uint32_t first, uint3
  * ran, and sentences the host ran. */
 int spm_hip_nbest_last_stats(const spm_hip_model *model, uint64_t *second_pass, uint64_t *host_path);
 
+/* BPE Encode of real text.  A BPE model is word-closed when every piece, of
+ * any type, is zero or more "▁" followed by chars other than "▁" (every model
+ * trained with split_by_whitespace is).  No merge then spans a "▁" that
+ * follows another char, so a sentence the first kernels flag (over 64 bytes)
+ * is cut there and its words are encoded independently, one per lane; the ids
+ * are the reference's.  *closed: the flag, computed at load from the pieces'
+ * strings (re-tagging pieces never changes it).  Works on a host-only handle;
+ * SPM_INVALID_ARGUMENT on a model that is not BPE. */
+int spm_hip_model_bpe_word_closed(const spm_hip_model *model, int *closed);
+/* Of the last blocking Encode of a BPE model on the handle: the flagged
+ * sentences (spm_hip_encode_stats.general_path, their sum) by the tier that
+ * finished them: the word tier, the one-sentence-per-wave tier (<= 1024
+ * bytes), the literal kernel.  The three counts and spm_hip_model_last_stats
+ * are published together when a blocking Encode ends, so the sum holds
+ * between a pair read with no other call on the handle in between; the
+ * asynchronous entry publishes neither.  Any pointer may be NULL. */
+int spm_hip_bpe_tier_last_stats(const spm_hip_model *model, uint64_t *word_tier, uint64_t *wave_tier,
+                                uint64_t *literal);
+
 /* Normalizer::Normalize (normalizer.cc:88-211) on host threads, batched:
  * raw CSR lines in, normalized CSR out.  out capacity: 3*in_off[n] + 3*n
  * bytes.  norm_to_orig is not produced.  num_threads <= 0 → hardware

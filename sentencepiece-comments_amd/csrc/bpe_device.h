@@ -1,13 +1,15 @@
-// Device-side pieces the BPE encode kernels share (bpe_kernels.hip: the batch
-// tiers, bpe_line.hip: one wave per line): the kernels' model tables, the
-// exact-match walk of the symbol trie, the fused pair probe and the wave
-// maximum over score keys.  Every definition is local to the including file.
+// Device-side pieces the BPE encode kernels share (bpe_kernels.hip and
+// bpe_words.hip: the batch tiers, bpe_line.hip: one wave per line): the
+// kernels' model tables, the exact-match walk of the symbol trie, the fused
+// pair probes, the packed char entries and the wave maximum over score keys.
+// Every definition is local to the including file.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "kernels.h"
 #include "sample_rng.h"
 
 namespace spm_amd {
@@ -62,6 +64,46 @@ struct BpeArgs {
   uint32_t *__restrict__ lane_len;
 };
 
+// The model tables, the batch's bytes and the slots as a launch struct of
+// kernels.h carries them (BpeLineArgs), and back.  The way back leaves what
+// only the lane kernel reads (scores, kinds, the key / value tables, the rank
+// fields, pipe_probes) and the per-call lists zero: the caller sets what its
+// kernel uses.
+__host__ __device__ inline BpeLineArgs BpeLineArgsOf(const BpeArgs &a) {
+  BpeLineArgs t{};
+  t.units = a.units;
+  t.values = a.values;
+  t.entry_piece = a.entry_piece;
+  t.entry_out = a.entry_out;
+  t.piece_out = a.piece_out;
+  t.pair_ent = a.pair_ent;
+  t.pair_mask = a.pair_mask;
+  t.root_base = a.root_base;
+  t.unk_id = a.unk_id;
+  t.irregular = a.irregular;
+  t.bytes = a.bytes;
+  t.slot_ids = a.slot_ids;
+  t.slot_len = a.slot_len;
+  return t;
+}
+__host__ __device__ inline BpeArgs BpeArgsOf(const BpeLineArgs &t) {
+  BpeArgs a{};
+  a.units = t.units;
+  a.values = t.values;
+  a.entry_piece = t.entry_piece;
+  a.entry_out = t.entry_out;
+  a.piece_out = t.piece_out;
+  a.pair_ent = t.pair_ent;
+  a.pair_mask = t.pair_mask;
+  a.root_base = t.root_base;
+  a.unk_id = t.unk_id;
+  a.irregular = t.irregular;
+  a.bytes = t.bytes;
+  a.slot_ids = t.slot_ids;
+  a.slot_len = t.slot_len;
+  return a;
+}
+
 // Exact-match walk of s[0:len) in the string trie; returns entry or -1.
 __device__ __forceinline__ int32_t ExactEntry(const BpeArgs &a, const uint8_t *s, uint32_t len) {
   uint32_t base = a.root_base, node = 0, u = 0;
@@ -103,6 +145,80 @@ __device__ __forceinline__ int32_t PairLookupFused(const BpeArgs &a, int32_t l, 
     if (e.x == 0xFFFFFFFFu && e.y == 0xFFFFFFFFu) return -1;
     h = (h + 1) & mask;
   }
+}
+
+// Two independent fused probes issued together (the merge's new neighbour
+// pairs (P, L) and (L, RR)): a miss on either side costs one more round.
+__device__ __forceinline__ void PairLookupFused2(const BpeArgs &a, int32_t l0, int32_t r0, bool en0, int32_t l1,
+                                                 int32_t r1, bool en1, int32_t *m0, uint32_t *k0, bool *u0,
+                                                 int32_t *m1, uint32_t *k1, bool *u1) {
+  const uint32_t mask = static_cast<uint32_t>(a.pair_mask);
+  bool go0 = en0 && l0 >= 0 && r0 >= 0, go1 = en1 && l1 >= 0 && r1 >= 0;
+  uint32_t h0 = go0 ? PairHash((static_cast<uint64_t>(static_cast<uint32_t>(l0)) << 32) | static_cast<uint32_t>(r0)) & mask : 0u;
+  uint32_t h1 = go1 ? PairHash((static_cast<uint64_t>(static_cast<uint32_t>(l1)) << 32) | static_cast<uint32_t>(r1)) & mask : 0u;
+  *m0 = *m1 = -1;
+  *k0 = *k1 = 0u;
+  *u0 = *u1 = false;
+  while (go0 || go1) {
+    uint4 e0 = make_uint4(0u, 0u, 0u, 0u), e1 = make_uint4(0u, 0u, 0u, 0u);
+    if (go0) e0 = a.pair_ent[h0];
+    if (go1) e1 = a.pair_ent[h1];
+    if (go0) {
+      if (e0.x == static_cast<uint32_t>(r0) && e0.y == static_cast<uint32_t>(l0)) {
+        *m0 = static_cast<int32_t>(e0.z & 0x7FFFFFFFu);
+        *k0 = e0.w;
+        *u0 = (e0.z >> 31) != 0;
+        go0 = false;
+      } else if (e0.x == 0xFFFFFFFFu && e0.y == 0xFFFFFFFFu) {
+        go0 = false;
+      } else {
+        h0 = (h0 + 1) & mask;
+      }
+    }
+    if (go1) {
+      if (e1.x == static_cast<uint32_t>(r1) && e1.y == static_cast<uint32_t>(l1)) {
+        *m1 = static_cast<int32_t>(e1.z & 0x7FFFFFFFu);
+        *k1 = e1.w;
+        *u1 = (e1.z >> 31) != 0;
+        go1 = false;
+      } else if (e1.x == 0xFFFFFFFFu && e1.y == 0xFFFFFFFFu) {
+        go1 = false;
+      } else {
+        h1 = (h1 + 1) & mask;
+      }
+    }
+  }
+}
+
+// (sym & 0xFFFF) | PieceToId << 16 of the char whose n bytes are w's low
+// bytes (low byte first), by an exact-match walk of the symbol trie: the
+// entries of the one-byte chars and of U+2581 that the lane-per-sentence and
+// lane-per-word kernels keep in LDS (both values < 2^15 on those paths).
+__device__ __forceinline__ uint32_t CharEntryPacked(const BpeArgs &a, uint32_t w, uint32_t n) {
+  uint32_t base = a.root_base, node = 0, u = 0;
+  bool ok = true;
+  for (uint32_t j = 0; j < n && ok; ++j) {
+    const uint32_t c = (w >> (8 * j)) & 0xFFu;
+    node = base ^ c;
+    u = c ? a.units[node] : 0u;
+    ok = c != 0 && (u & 0xFFu) == c;
+    base = u >> 9;
+  }
+  const int32_t e = ok && (u & 0x100u) ? a.values[node] : -1;
+  const int32_t sym = e >= 0 ? a.entry_piece[e] : -1;
+  const int32_t out = e >= 0 ? a.entry_out[e] : a.unk_id;
+  return (static_cast<uint32_t>(sym) & 0xFFFFu) | (static_cast<uint32_t>(out) << 16);
+}
+
+// Nothing to do when an earlier step of an asynchronous chain failed or the
+// batch exceeds the caller's capacity (the slots are sized by it): status
+// bit 1 (of status[kStError]) makes the compaction skip too.
+__device__ __forceinline__ bool BpeSkip(const BpeArgs &a) {
+  if ((a.chain && *a.chain) || a.off[a.n] > a.capacity) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.status[kStError], 2u);
+    return true;
+  }
+  return false;
 }
 
 // BPE-dropout of one sentence: its key in the sampler's counter-based stream

@@ -25,10 +25,18 @@
 //   Covers sentences of <= 64 bytes on models without USER_DEFINED pieces;
 //   pushes of UNUSED pieces (which need the rev_merge resegmentation) and
 //   chars outside the vocabulary on "irregular" models flag the sentence.
+// bpe_split_kernel (bpe_words.hip) — ahead of bpe_fast_kernel: the lane / half
+//   kernel's rest list, one entry per thread; sentences of > 64 bytes are
+//   flagged here a block at a time, bpe_fast_kernel sees only the others.
+// bpe_words_kernel / bpe_wave_kernel (bpe_words.hip) — the tiers of real
+//   text, over the sentences the kernels above flagged: one sentence per
+//   wavefront, cut into independent words that are encoded one per lane
+//   (word-closed models), or encoded whole by the wave (<= 1024 bytes).
 // bpe_general_kernel — the reference algorithm literally, one sentence per
 //   lane: symbol list, binary-heap agenda with the same comparator, stale
 //   check by size, string lookups by exact-match walks of the concatenated
-//   bytes, rev_merge (last push wins) and the recursive resegment.
+//   bytes, rev_merge (last push wins) and the recursive resegment.  It takes
+//   what the two text tiers hand on.
 // bpe_raw_kernel / bpe_small_kernel (bpe_line.hip) — the small host calls, not
 //   a tier of the batch path: one launch per call, one sentence per
 //   wavefront, a lane owns several symbols (state in LDS), sentences of <=
@@ -60,17 +68,6 @@ constexpr uint8_t kPieceOther = 0, kPieceUserDefined = 1, kPieceUnused = 2;
 // ntok[i] of a sentence bpe_lane_kernel encoded: bit 31 set, bits 8-30 the
 // tile-local index of its first token, bits 0-7 its token count (<= 32).
 constexpr uint32_t kLaneTok = 0x80000000u;
-
-// Nothing to do when an earlier step of an asynchronous chain failed or the
-// batch exceeds the caller's capacity (the slots are sized by it): status
-// bit 1 makes the compaction skip too.
-__device__ __forceinline__ bool BpeSkip(const BpeArgs &a) {
-  if ((a.chain && *a.chain) || a.off[a.n] > a.capacity) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.status[kStError], 2u);
-    return true;
-  }
-  return false;
-}
 
 __device__ __forceinline__ int32_t PairLookup(const BpeArgs &a, int32_t l, int32_t r) {
   if (l < 0 || r < 0) return -1;
@@ -273,50 +270,7 @@ __global__ __launch_bounds__(256) void bpe_half_kernel(BpeArgs a, uint32_t *__re
   }
 }
 
-// Two independent fused probes issued together (the merge's new neighbour
-// pairs (P, L) and (L, RR)): a miss on either side costs one more round.
-__device__ __forceinline__ void PairLookupFused2(const BpeArgs &a, int32_t l0, int32_t r0, bool en0, int32_t l1,
-                                                 int32_t r1, bool en1, int32_t *m0, uint32_t *k0, bool *u0,
-                                                 int32_t *m1, uint32_t *k1, bool *u1) {
-  const uint32_t mask = static_cast<uint32_t>(a.pair_mask);
-  bool go0 = en0 && l0 >= 0 && r0 >= 0, go1 = en1 && l1 >= 0 && r1 >= 0;
-  uint32_t h0 = go0 ? PairHash((static_cast<uint64_t>(static_cast<uint32_t>(l0)) << 32) | static_cast<uint32_t>(r0)) & mask : 0u;
-  uint32_t h1 = go1 ? PairHash((static_cast<uint64_t>(static_cast<uint32_t>(l1)) << 32) | static_cast<uint32_t>(r1)) & mask : 0u;
-  *m0 = *m1 = -1;
-  *k0 = *k1 = 0u;
-  *u0 = *u1 = false;
-  while (go0 || go1) {
-    uint4 e0 = make_uint4(0u, 0u, 0u, 0u), e1 = make_uint4(0u, 0u, 0u, 0u);
-    if (go0) e0 = a.pair_ent[h0];
-    if (go1) e1 = a.pair_ent[h1];
-    if (go0) {
-      if (e0.x == static_cast<uint32_t>(r0) && e0.y == static_cast<uint32_t>(l0)) {
-        *m0 = static_cast<int32_t>(e0.z & 0x7FFFFFFFu);
-        *k0 = e0.w;
-        *u0 = (e0.z >> 31) != 0;
-        go0 = false;
-      } else if (e0.x == 0xFFFFFFFFu && e0.y == 0xFFFFFFFFu) {
-        go0 = false;
-      } else {
-        h0 = (h0 + 1) & mask;
-      }
-    }
-    if (go1) {
-      if (e1.x == static_cast<uint32_t>(r1) && e1.y == static_cast<uint32_t>(l1)) {
-        *m1 = static_cast<int32_t>(e1.z & 0x7FFFFFFFu);
-        *k1 = e1.w;
-        *u1 = (e1.z >> 31) != 0;
-        go1 = false;
-      } else if (e1.x == 0xFFFFFFFFu && e1.y == 0xFFFFFFFFu) {
-        go1 = false;
-      } else {
-        h1 = (h1 + 1) & mask;
-      }
-    }
-  }
-}
-
-constexpr int kLB = 128;         // lanes (sentences) per tile
+constexpr int kLB = 128;        // lanes (sentences) per tile
 // Chars per sentence on the lane path: 34 covers the synthetic ~25-char
 // sentences' longest (33 chars with the dummy prefix), at 8 tiles per CU
 // (LDS 19.9 KB per tile); live-symbol masks are 64-bit.
@@ -362,26 +316,8 @@ __global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__re
   if (BpeSkip(a)) return;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  {
-    // Exact-match walk of the bytes of `w` (low byte first, n of them).
-    auto entry_packed = [&](uint32_t w, uint32_t n) -> uint32_t {
-      uint32_t base = a.root_base, node = 0, u = 0;
-      bool ok = true;
-      for (uint32_t j = 0; j < n && ok; ++j) {
-        const uint32_t c = (w >> (8 * j)) & 0xFFu;
-        node = base ^ c;
-        u = c ? a.units[node] : 0u;
-        ok = c != 0 && (u & 0xFFu) == c;
-        base = u >> 9;
-      }
-      const int32_t e = ok && (u & 0x100u) ? a.values[node] : -1;
-      const int32_t sym = e >= 0 ? a.entry_piece[e] : -1;
-      const int32_t out = e >= 0 ? a.entry_out[e] : a.unk_id;
-      return (static_cast<uint32_t>(sym) & 0xFFFFu) | (static_cast<uint32_t>(out) << 16);
-    };
-    for (uint32_t c = static_cast<uint32_t>(tid); c < 256; c += kLB) lds_c1[c] = entry_packed(c, 1);
-    if (tid == 0) lds_ws = entry_packed(0x8196E2u, 3);
-  }  // (the first tile's sort barriers publish the table)
+  for (uint32_t c = static_cast<uint32_t>(tid); c < 256; c += kLB) lds_c1[c] = CharEntryPacked(a, c, 1);
+  if (tid == 0) lds_ws = CharEntryPacked(a, 0x8196E2u, 3);  // (the first tile's sort barriers publish the table)
   for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * kLB; base < a.n;
        base += static_cast<uint64_t>(gridDim.x) * kLB) {
     // Counting sort of the tile's sentences by byte length (each wave's lanes
@@ -1256,6 +1192,19 @@ int LoadBpe(spm_hip_model *m, std::string *err) {
   // and the unk id are < V as well).
   m->bpe.lane_ok = V <= 32767;
   m->bpe.rank_ids = !rank_piece.empty();
+  // Word-closed: no piece, of any type, holds a "▁" after another char.
+  m->bpe.word_closed = true;
+  for (const auto &p : pieces) {
+    const std::string &s = p.piece;
+    bool other = false;
+    for (size_t q = 0; q < s.size();) {
+      const size_t l = std::min<size_t>(OneCharLen(static_cast<uint8_t>(s[q])), s.size() - q);
+      const bool ws = s.compare(q, l, "\xE2\x96\x81") == 0;
+      if (ws && other) m->bpe.word_closed = false;
+      if (!ws) other = true;
+      q += l;
+    }
+  }
   m->max_piece_chars = 0;
   m->up.root_base = DoubleArray::Base(m->trie.units[0]);
   m->up.unk_id = m->unk_id;
@@ -1362,9 +1311,12 @@ hipError_t LaunchBpeCompact(const uint64_t *off, uint64_t n, const uint32_t *nto
 
 // Encode of one batch: bpe_lane_kernel (one sentence per lane; bpe_half_kernel,
 // two sentences per wave, for vocabularies of >= 32768 pieces) + bpe_fast_kernel
-// for the rest, then the general kernel on the flagged sentences with a
-// device-side count (a fixed pool of lane slabs, one lane with the whole pool
-// for longer sentences), scan + compaction.  No host synchronization unless
+// for the rest (of <= 64 bytes: bpe_split_kernel flags the longer ones before
+// it); the flagged sentences then go through the word tier and the
+// wave tier (bpe_words.hip), and what those hand on, in a second device-side
+// list, to the general kernel with a device-side count (a fixed pool of lane
+// slabs, one lane with the whole pool for longer sentences); scan +
+// compaction.  No host synchronization unless
 // c.host_sized (general kernel over every sentence, scratch sized from the
 // longest sentence: models with user-defined symbols, force_general).
 // c.drop (BPE-dropout): bpe_dropout_kernel (bpe_dropout.hip) in place of the
@@ -1407,6 +1359,13 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
   static const bool kFastOnly = [] {
     const char *e = std::getenv("SPM_HIP_BPE_FAST_ONLY");
     return e && std::atoi(e) != 0;
+  }();
+  // A/B knob: SPM_HIP_BPE_TEXT=0 hands every flagged sentence to the literal
+  // kernel (no word tier, no wave tier); 2 runs the wave tier without the
+  // word tier.
+  static const int kTextKnob = [] {
+    const char *e = std::getenv("SPM_HIP_BPE_TEXT");
+    return e ? std::atoi(e) : 1;
   }();
   const BpeDropout drop = c.drop ? *c.drop : BpeDropout{};
   auto general = [&](dim3 grid, const GenBpeArgs &g) {
@@ -1478,7 +1437,7 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
       d.seed = drop.seed;
       d.index_base = drop.index_base;
       d.rest = kShortKnob ? ws->w_rest.as<uint32_t>() : nullptr;
-      d.rest_count = kShortKnob ? status + 8 : nullptr;
+      d.rest_count = kShortKnob ? status + kStBpeRest : nullptr;
       BPE_TRY(LaunchBpeDropout(d, st));
     } else if (kFastOnly) {
       // (nothing first: bpe_fast_kernel below takes every sentence)
@@ -1494,19 +1453,49 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
       }();
       const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(tiles, 1u << 20)));
       if (m->bpe.rank_ids && kRankIdsKnob)
-        hipLaunchKernelGGL(bpe_lane_kernel<true>, grid, dim3(kLB), 0, st, a, ws->w_rest.as<uint32_t>(), status + 8);
+        hipLaunchKernelGGL(bpe_lane_kernel<true>, grid, dim3(kLB), 0, st, a, ws->w_rest.as<uint32_t>(), status + kStBpeRest);
       else
-        hipLaunchKernelGGL(bpe_lane_kernel<false>, grid, dim3(kLB), 0, st, a, ws->w_rest.as<uint32_t>(), status + 8);
+        hipLaunchKernelGGL(bpe_lane_kernel<false>, grid, dim3(kLB), 0, st, a, ws->w_rest.as<uint32_t>(), status + kStBpeRest);
     } else {
       const uint64_t hblocks64 = (((n + 1) / 2) * 64 + 255) / 256;
       const unsigned hblocks = static_cast<unsigned>(std::min<uint64_t>(hblocks64, 1u << 20));
-      hipLaunchKernelGGL(bpe_half_kernel, dim3(hblocks), dim3(256), 0, st, a, ws->w_rest.as<uint32_t>(), status + 8);
+      hipLaunchKernelGGL(bpe_half_kernel, dim3(hblocks), dim3(256), 0, st, a, ws->w_rest.as<uint32_t>(), status + kStBpeRest);
     }
     BPE_TRY(hipGetLastError());
+    // The text tiers' launch struct; with them the rest list is split first:
+    // its sentences over 64 bytes are flagged a block at a time, and
+    // bpe_fast_kernel sees the others alone.
+    const bool text = !c.drop && !m->bpe.has_user_defined && kTextKnob != 0;
+    BpeTextLaunch t{};
+    if (text) {
+      BPE_TRY(ws->w_bpe_wave.Reserve(nn * 4));
+      BPE_TRY(ws->w_bpe_lit.Reserve(nn * 4));
+      t.t = BpeLineArgsOf(a);
+      t.off = a.off;
+      t.n = n;
+      t.ntok = a.ntok;
+      t.status = status;
+      t.capacity = cap;
+      t.chain = c.out_status;
+      t.flagged = ws->w_flagged.as<uint32_t>();
+      t.wave_list = ws->w_bpe_wave.as<uint32_t>();
+      t.rest = ws->w_rest.as<uint32_t>();
+      t.fast_list = t.wave_list;                // (the fast kernel has read it before the word tier starts)
+      t.wave_rest = ws->w_rest.as<uint32_t>();  // (the split kernel has consumed its list)
+      t.word_rest = t.wave_rest;                // (and the word tier its own before the wave tier starts)
+      t.literal = ws->w_bpe_lit.as<uint32_t>();
+      t.word_closed = m->bpe.word_closed && m->bpe.lane_ok && kTextKnob != 2 ? 1 : 0;
+    }
     if (!c.drop) {
+      const uint32_t *fast_list = ws->w_rest.as<uint32_t>(), *fast_count = status + kStBpeRest;
+      if (text && !kFastOnly) {
+        BPE_TRY(LaunchBpeSplit(t, st));
+        fast_list = t.fast_list;
+        fast_count = status + kStBpeFast;
+      }
       const uint64_t blocks64 = (n * 64 + 255) / 256;
       hipLaunchKernelGGL(bpe_fast_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>(blocks64, 8192u))), dim3(256),
-                         0, st, a, kFastOnly ? nullptr : ws->w_rest.as<uint32_t>(), status + 8);
+                         0, st, a, kFastOnly ? nullptr : fast_list, fast_count);
       BPE_TRY(hipGetLastError());
     }
     timed_fast = slot >= 0;  // the timed span ends after the output compaction below
@@ -1517,7 +1506,16 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
     uint32_t *ovf = ws->w_ovf.as<uint32_t>();
     const int32_t ud = m->bpe.has_user_defined ? 1 : 0;
     if (slot >= 0) BPE_TRY(hipEventRecord(ws->ev[0], st));
-    GenBpeArgs g1{a, ws->w_flagged.as<uint32_t>(), status + kStFlagged, 0, ws->w_scratch.as<uint8_t>(), gp.slab,
+    // The flagged sentences: the word tier (word-closed models whose ids fit
+    // the lane columns' 16 bits), the wave tier, and what they hand on, in a
+    // second device-side list, to the literal kernel.
+    const uint32_t *lit_list = ws->w_flagged.as<uint32_t>(), *lit_count = status + kStFlagged;
+    if (text) {
+      BPE_TRY(LaunchBpeText(t, st));
+      lit_list = t.literal;
+      lit_count = status + kStBpeLiteral;
+    }
+    GenBpeArgs g1{a, lit_list, lit_count, 0, ws->w_scratch.as<uint8_t>(), gp.slab,
                   gp.small_nb, status + kStError, ud, ovf, status + kStOverflow, gp.lanes,
                   drop.threshold, drop.seed, drop.index_base};
     general(dim3((gp.lanes + 63) / 64), g1);

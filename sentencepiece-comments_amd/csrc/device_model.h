@@ -44,6 +44,7 @@ struct EncodeWorkspace {
   DevBuf w_slot_ids, w_slot_len, w_tprefix;
   DevBuf w_ctl, w_slot2_ids, w_slot2_len, w_ntok, w_cnt, w_bp, w_flagged, w_ovf, w_scan, w_scratch,
       w_rest;
+  DevBuf w_bpe_wave, w_bpe_lit;  // BPE text tiers: the wave tier's list, the literal kernel's
   DevBuf w_bpn;  // wide-char kernel: trie unit of the best node ending at each byte position
   // Wave-cooperative kernel (coop_encode.hip): per-byte length masks and
   // chosen lnode lengths, and its list of sentences left to the general kernel.
@@ -220,6 +221,9 @@ struct spm_hip_model {
   std::vector<std::unique_ptr<spm_amd::EncodeWorkspace>> host_pool;
   spm_hip_encode_stats last_stats{};  // of the last completed encode call (pool_mu)
   uint64_t nbest_second = 0, nbest_host = 0;  // of the last n-best call (pool_mu)
+  // Of the last blocking BPE Encode: flagged sentences by the tier that
+  // finished them (pool_mu); their sum is last_stats.general_path.
+  uint64_t bpe_word_tier = 0, bpe_wave_tier = 0, bpe_literal = 0;
   std::atomic<uint32_t> nbest_hyps1{0}, nbest_hyps2{0};  // spm_hip_model_set_nbest_max_hyps
   int device = 0;
 };

@@ -79,6 +79,10 @@ struct BpeDevice {
   // (pieces in descending-score order with distinct scores, as trained BPE
   // models are): the lane kernel skips the table load.  -1: use the table.
   int32_t rank_base = -1;
+  // Every piece string is "▁"* followed by chars other than "▁": a sentence
+  // splits into independent words (bpe_words.hip).  Set at load from the
+  // strings alone; re-tagging pieces never changes it.
+  bool word_closed = false;
 };
 
 }  // namespace spm_amd

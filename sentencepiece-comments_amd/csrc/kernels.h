@@ -23,6 +23,16 @@ enum : int {
   kStCoopQueue = 7, // the cooperative list kernel's work queue (next list entry)
   kStCoopLong = 8,  // coop partition: long sentences (taken first)
   kStCoopShort = 9, // coop partition: the others
+  // BPE encode (the cooperative kernels' words are free there):
+  kStBpeRest = 8,   // sentences the lane / half kernel left to the kernels after it
+  kStBpeFast = 9,   // of those, the ones bpe_split_kernel lists for bpe_fast_kernel
+  // BPE text tiers (bpe_words.hip) over the flagged sentences:
+  kStBpeWaveList = 10, // sentences the word tier handed to the wave tier
+  kStBpeWaveRest = 11, // wave tier: sentences its short-slab pass left to the full one
+  kStBpeLiteral = 12,  // sentences handed on to bpe_general_kernel
+  kStBpeWordDone = 13, // sentences the word tier finished
+  kStBpeWaveDone = 14, // sentences the wave tier finished
+  kStBpeWordRest = 15, // word tier: sentences its short-state launch left to the full one
   kStWords = 16
 };
 
@@ -536,6 +546,48 @@ struct BpeDropoutLaunch {
   uint32_t *rest, *rest_count;
 };
 hipError_t LaunchBpeDropout(const BpeDropoutLaunch &d, hipStream_t st);
+
+// BPE text tiers (bpe_words.hip), between the first kernels and
+// bpe_general_kernel: they consume `flagged` (status[kStFlagged] entries).
+// word_closed (every piece is "▁"* followed by non-"▁" chars, and ids fit 16
+// bits): bpe_words_kernel cuts a sentence of > 64 bytes where a "▁" follows
+// another char and encodes the words one per lane (<= kBpeWordChars chars;
+// longer words by the whole wave, <= kBpeLineMaxBytes bytes).  Sentences it
+// does not split (their OneCharLen walk is not their non-continuation bytes)
+// go to wave_list.  bpe_wave_kernel then takes wave_list (without the word
+// tier: flagged) one sentence per wave, <= kBpeLineMaxBytes bytes, the short
+// ones first (kBpeDropShortBytes, the others through wave_rest).  What
+// neither finishes is listed in `literal` (status[kStBpeLiteral] entries);
+// all three lists hold up to n entries.  t: the model's tables as in
+// BpeDropoutLaunch.
+constexpr int kBpeWordChars = 16;  // the word tier's lane bound
+struct BpeTextLaunch {
+  BpeLineArgs t;
+  const uint64_t *off;
+  uint64_t n;
+  uint32_t *ntok;
+  uint32_t *status;          // kStWords
+  uint64_t capacity;         // caller's bound on off[n]
+  const uint32_t *chain;     // asynchronous chain status (nullable)
+  uint32_t *flagged;
+  uint32_t *wave_list, *wave_rest, *literal;
+  // LaunchBpeSplit: the lane / half kernel's rest list (status[kStBpeRest]
+  // entries) and the list it leaves to bpe_fast_kernel (status[kStBpeFast]).
+  // fast_list may be wave_list's buffer: the fast kernel has read it before
+  // the word tier starts.
+  const uint32_t *rest;
+  uint32_t *fast_list;
+  // Word tier: sentences with a word over the lane bound and over
+  // kBpeDropShortBytes bytes, for its second launch.  May be wave_rest's
+  // buffer: the word tier has finished before the wave tier starts.
+  uint32_t *word_rest;
+  int32_t word_closed;
+};
+hipError_t LaunchBpeText(const BpeTextLaunch &d, hipStream_t st);
+// bpe_split_kernel, between the lane / half kernel and bpe_fast_kernel: the
+// sentences of `rest` over 64 bytes are flagged (as bpe_fast_kernel flags
+// them, but a block at a time), the others listed in fast_list for it.
+hipError_t LaunchBpeSplit(const BpeTextLaunch &d, hipStream_t st);
 
 // Resident service kernel for small calls (coop_service_kernel): one block
 // polls `box` in pinned coherent host memory; the host writes `call` and

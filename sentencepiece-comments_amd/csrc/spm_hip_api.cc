@@ -512,7 +512,11 @@ int LongestSentence(const uint64_t *d_off, uint64_t n, hipStream_t st, uint32_t 
 // The tier counts and kernel times of a blocking call that has been waited
 // for: `flagged` sentences left the fast tier, or all n when the call ran
 // host-sized.  Publishes the call's stats.
-int PublishTierStats(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n, bool host_sized, uint32_t flagged) {
+// bpe_done (BPE Encode, else nullptr): the flagged sentences the word and the
+// wave tier finished; published with the stats under one lock, so that
+// their sum with the literal kernel's share is this call's general_path.
+int PublishTierStats(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n, bool host_sized, uint32_t flagged,
+                     const uint64_t *bpe_done = nullptr) {
   ws->stats.sentences = n;
   ws->stats.general_path = host_sized ? n : flagged;
   if (m->timing && ws->last_slot >= 0) {
@@ -521,7 +525,15 @@ int PublishTierStats(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n,
     if (ws->stats.general_path) SPM_HIP_TRY(hipEventElapsedTime(&ws->stats.general_kernel_ms, ws->ev[0], ws->ev[1]));
     ws->tcount = 0;  // consumed here; the ring is for the asynchronous entry point
   }
-  spm_amd::PublishStats(m, ws->stats);
+  if (!bpe_done) {
+    spm_amd::PublishStats(m, ws->stats);
+    return SPM_OK;
+  }
+  std::lock_guard<std::mutex> lk(m->pool_mu);
+  m->last_stats = ws->stats;
+  m->bpe_word_tier = host_sized ? 0 : bpe_done[0];
+  m->bpe_wave_tier = host_sized ? 0 : bpe_done[1];
+  m->bpe_literal = ws->stats.general_path - m->bpe_word_tier - m->bpe_wave_tier;
   return SPM_OK;
 }
 
@@ -1004,9 +1016,12 @@ int EncodeBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t
   if (c.host_sized && (rc = LongestSentence(d_off, n, st, &c.max_nb)) != SPM_OK) return rc;
   ws->stats = spm_hip_encode_stats{};
   if ((rc = EncodeEnqueue(m, ws, c)) != SPM_OK) return rc;
-  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, ws->w_ctl.ptr, 4 * (spm_amd::kStCoopRest + 1), hipMemcpyDeviceToHost, st));
+  SPM_HIP_TRY(hipMemcpyAsync(ws->pinned, ws->w_ctl.ptr, 4 * spm_amd::kStWords, hipMemcpyDeviceToHost, st));
   SPM_HIP_TRY(hipStreamSynchronize(st));
   uint32_t flagged = ws->pinned[spm_amd::kStFlagged], err = ws->pinned[spm_amd::kStError];
+  // BPE Encode: the flagged sentences the word and the wave tier finished.
+  const bool bpe_tiers = m->model_type == spm_amd::kBpe && !drop;
+  const uint64_t bpe_done[2] = {ws->pinned[spm_amd::kStBpeWordDone], ws->pinned[spm_amd::kStBpeWaveDone]};
   if (err && !c.host_sized) {
     c.host_sized = true;
     rc = LongestSentence(d_off, n, st, &c.max_nb);
@@ -1019,7 +1034,7 @@ int EncodeBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t
   }
   if (err) return Fail(SPM_INTERNAL, "general encode path: scratch overflow");
   ws->stats.coop_rest = c.host_sized ? 0 : ws->pinned[spm_amd::kStCoopRest];
-  return PublishTierStats(m, ws, n, c.host_sized, flagged);
+  return PublishTierStats(m, ws, n, c.host_sized, flagged, bpe_tiers ? bpe_done : nullptr);
 }
 
 // Lazy device tables of the normalizer (charsmap blob, user-defined trie).
@@ -1241,7 +1256,8 @@ void EncodeWorkspace::Release() {
                     &w_scratch, &w_rest, &w_nlen, &w_nscan, &w_ecount, &w_escan, &w_dfirst, &w_dsum, &w_dctl, &w_bfsum, &w_bfctl, &h_dids, &h_dtok, &h_dout, &h_doff, &h_dbegin, &w_tids, &w_tlen, &w_ttok,
                     &h_in, &h_off, &h_ids, &h_len, &h_tok, &w_small, &w_bpn, &w_cpv, &w_cnd, &w_crest, &w_cpart, &w_salpha, &w_smask, &w_lpath, &w_lscore, &w_llogz,
                     &w_nb_ctl, &w_nb_npaths, &w_nb_stage, &w_nb_ntok, &w_nb_score, &w_nb_ids, &w_nb_len, &w_nb_hids,
-                    &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore, &w_wc_count, &w_wc_first, &w_wc_sent, &w_wc_next, &w_vstat, &w_vcount})
+                    &w_nb_hlen, &w_nb_ovf2, &w_nb_poff, &w_nb_ptok, &w_nb_toff, &w_nb_oscore, &w_wc_count, &w_wc_first, &w_wc_sent, &w_wc_next, &w_vstat, &w_vcount,
+                    &w_bpe_wave, &w_bpe_lit})
     b->Release();
   if (pinned) (void)hipHostFree(pinned);
   pinned = nullptr;
@@ -1258,7 +1274,9 @@ void EncodeWorkspace::Release() {
 
 static hipError_t NewWorkspace(bool own_stream, std::unique_ptr<EncodeWorkspace> *out) {
   auto ws = std::make_unique<EncodeWorkspace>();
-  hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&ws->pinned), 64);
+  // (16 read-back words: a call's status words, or the few slots other calls use)
+  static_assert(4 * spm_amd::kStWords == 64, "EncodeBlocking reads every status word back into pinned");
+  hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&ws->pinned), 4 * spm_amd::kStWords);
   if (e == hipSuccess && own_stream) e = hipStreamCreateWithFlags(&ws->own_stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     ws->Release();
@@ -3488,6 +3506,22 @@ int spm_hip_nbest_last_stats(const spm_hip_model *m, uint64_t *second_pass, uint
   std::lock_guard<std::mutex> lk(const_cast<spm_hip_model *>(m)->pool_mu);
   if (second_pass) *second_pass = m->nbest_second;
   if (host_path) *host_path = m->nbest_host;
+  return SPM_OK;
+}
+
+int spm_hip_model_bpe_word_closed(const spm_hip_model *m, int *closed) {
+  if (!m || !closed) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (m->model_type != spm_amd::kBpe) return Fail(SPM_INVALID_ARGUMENT, "not a BPE model");
+  *closed = m->bpe.word_closed ? 1 : 0;
+  return SPM_OK;
+}
+
+int spm_hip_bpe_tier_last_stats(const spm_hip_model *m, uint64_t *word_tier, uint64_t *wave_tier, uint64_t *literal) {
+  if (!m) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  std::lock_guard<std::mutex> lk(const_cast<spm_hip_model *>(m)->pool_mu);
+  if (word_tier) *word_tier = m->bpe_word_tier;
+  if (wave_tier) *wave_tier = m->bpe_wave_tier;
+  if (literal) *literal = m->bpe_literal;
   return SPM_OK;
 }
 

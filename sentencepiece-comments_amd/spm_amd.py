@@ -53,7 +53,7 @@ EXPORTED = [
     "spm_hip_entropy_batch", "spm_hip_entropy_batch_host", "spm_hip_sample_encode_and_score_batch",
     "spm_hip_sample_encode_and_score_batch_host", "spm_hip_sample_seed",
     "spm_hip_nbest_encode_batch", "spm_hip_nbest_encode_batch_host", "spm_hip_model_set_nbest_max_hyps",
-    "spm_hip_nbest_last_stats",
+    "spm_hip_nbest_last_stats", "spm_hip_model_bpe_word_closed", "spm_hip_bpe_tier_last_stats",
     "spm_hip_model_set_piece_types", "spm_hip_model_get_piece_types", "spm_hip_model_set_vocabulary",
     "spm_hip_model_reset_vocabulary", "spm_hip_count_ids", "spm_hip_count_ids_host",
     "spm_hip_model_byte_fallback", "spm_hip_finalize_ids_bytes", "spm_hip_finalize_ids_bytes_async",
@@ -243,6 +243,8 @@ def lib():
                                                       ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_model_set_nbest_max_hyps.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32]
         L.spm_hip_nbest_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]
+        L.spm_hip_model_bpe_word_closed.argtypes = [P, ctypes.POINTER(ctypes.c_int)]
+        L.spm_hip_bpe_tier_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_device_peak_reset.restype = None
         L.spm_hip_decode_batch.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, ctypes.POINTER(U64), P]
         L.spm_hip_decode_batch_async.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, P, P]
@@ -852,6 +854,20 @@ class DeviceModel:
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         _check(self._L.spm_hip_nbest_last_stats(self.h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    def bpe_word_closed(self):
+        """Whether every piece of the BPE model is "▁"* followed by other
+        chars, so that Encode may cut sentences into independent words."""
+        c = ctypes.c_int()
+        _check(self._L.spm_hip_model_bpe_word_closed(self.h, ctypes.byref(c)))
+        return bool(c.value)
+
+    def bpe_tier_stats(self):
+        """(word_tier, wave_tier, literal): the flagged sentences of the last
+        blocking BPE Encode by the tier that finished them."""
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._L.spm_hip_bpe_tier_last_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
 
     def encode_normalized(self, sentences):
         buf, off = to_csr(sentences)
