@@ -464,6 +464,17 @@ int spm_hip_model_bpe_word_closed(const spm_hip_model *model, int *closed);
  * asynchronous entry publishes neither.  Any pointer may be NULL. */
 int spm_hip_bpe_tier_last_stats(const spm_hip_model *model, uint64_t *word_tier, uint64_t *wave_tier,
                                 uint64_t *literal);
+/* BPE models with USER_DEFINED pieces: Encode flags every sentence
+ * (general_path = the batch; fast_variant stays 0) and runs the frozen-symbol
+ * tier, one sentence per wave: the longest user-defined piece at each symbol
+ * start is one symbol that never merges.  Of the last blocking Encode on the
+ * handle: the sentences that tier finished and the ones it handed on to the
+ * literal kernel (over 1024 bytes, an OneCharLen walk that is not the
+ * non-continuation bytes, a pushed UNUSED piece, a char outside an irregular
+ * vocabulary); both are part of the third count above.  Both 0 for any other
+ * model, for BPE-dropout, under force_general and with SPM_HIP_BPE_FROZEN=0.
+ * Published with spm_hip_bpe_tier_last_stats.  Any pointer may be NULL. */
+int spm_hip_bpe_frozen_last_stats(const spm_hip_model *model, uint64_t *taken, uint64_t *handed_on);
 
 /* Normalizer::Normalize (normalizer.cc:88-211) on host threads, batched:
  * raw CSR lines in, normalized CSR out.  out capacity: 3*in_off[n] + 3*n

@@ -1188,6 +1188,44 @@ int LoadBpe(spm_hip_model *m, std::string *err) {
   m->bpe.pair_mask = cap - 1;
   m->bpe.irregular = irregular;
   m->bpe.has_user_defined = !m->user_defined.empty();
+  // The frozen-symbol tier's matcher (bpe_frozen.hip): the user-defined pieces
+  // alone in a double array of their own, behind the 256-bit set of the bytes
+  // they start with.  The tier needs every such piece to be whole chars
+  // without a NUL byte (a match then ends where a char ends); any other model
+  // keeps the host-sized literal pass, as does SPM_HIP_BPE_FROZEN=0 (A/B knob).
+  // Re-tagging exchanges NORMAL and UNUSED only, so this set never changes.
+  std::vector<uint32_t> ud_image;
+  m->bpe.frozen_ok = false;
+  if (m->bpe.has_user_defined) {
+    static const bool kFrozenKnob = [] {
+      const char *e = std::getenv("SPM_HIP_BPE_FROZEN");
+      return !e || std::atoi(e) != 0;
+    }();
+    bool whole = kFrozenKnob;
+    std::vector<std::pair<std::string, int32_t>> ud_keys;
+    ud_image.assign(8, 0u);
+    for (const std::string &u : m->user_defined) {  // (sorted)
+      for (size_t q = 0; q < u.size() && whole;) {
+        const uint8_t c = static_cast<uint8_t>(u[q]);
+        const size_t l = OneCharLen(c);
+        if (c == 0 || (c & 0xC0u) == 0x80u || q + l > u.size()) whole = false;
+        for (size_t j = 1; j < l && whole; ++j)
+          if ((static_cast<uint8_t>(u[q + j]) & 0xC0u) != 0x80u) whole = false;
+        q += l;
+      }
+      const uint8_t c0 = static_cast<uint8_t>(u[0]);
+      ud_image[c0 >> 5] |= 1u << (c0 & 31u);
+      ud_keys.emplace_back(u, 1);
+    }
+    if (whole) {
+      DoubleArray da;
+      if (!BuildDoubleArray(std::move(ud_keys), &da, err)) return SPM_RESOURCE_EXHAUSTED;
+      m->bpe.ud_units = static_cast<uint32_t>(da.units.size());
+      m->bpe.ud_root = DoubleArray::Base(da.units[0]);
+      ud_image.insert(ud_image.end(), da.units.begin(), da.units.end());
+      m->bpe.frozen_ok = true;
+    }
+  }
   // bpe_lane_kernel keeps symbol and merged ids as int16 (PieceToId values
   // and the unk id are < V as well).
   m->bpe.lane_ok = V <= 32767;
@@ -1222,6 +1260,7 @@ int LoadBpe(spm_hip_model *m, std::string *err) {
       !up(&m->bpe.piece_out, piece_out.data(), V * 4) ||
       !up(&m->bpe.pair_keys, hk.data(), cap * 8) || !up(&m->bpe.pair_vals, hv.data(), cap * 4) ||
       !up(&m->bpe.pair_ent, he.data(), cap * 16) ||
+      (m->bpe.frozen_ok && !up(&m->bpe.ud, ud_image.data(), ud_image.size() * 4)) ||
       (!rank_piece.empty() && !up(&m->bpe.rank_piece, rank_piece.data(), rank_piece.size() * 2))) {
     *err = "device upload failed";
     return SPM_INTERNAL;
@@ -1319,6 +1358,9 @@ hipError_t LaunchBpeCompact(const uint64_t *off, uint64_t n, const uint32_t *nto
 // compaction.  No host synchronization unless
 // c.host_sized (general kernel over every sentence, scratch sized from the
 // longest sentence: models with user-defined symbols, force_general).
+// Models with user-defined symbols (BpeDevice::frozen_ok): bpe_frozen_kernel
+// (bpe_frozen.hip) over every sentence in place of all of the above, then the
+// literal kernels over the list it hands on.
 // c.drop (BPE-dropout): bpe_dropout_kernel (bpe_dropout.hip) in place of the
 // lane / half / fast kernels and bpe_general_kernel<true> for what it flags.
 int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::string *err) {
@@ -1401,11 +1443,18 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
     BPE_TRY(hipGetLastError());
     if (slot >= 0) BPE_TRY(hipEventRecord(ws->ev[1], st));
   } else if (n) {
+    // Models with user-defined symbols: no first kernel, no bpe_fast_kernel and
+    // no text tier; the frozen-symbol tier (bpe_frozen.hip), then the literal
+    // kernels over what it hands on.  (BPE-dropout of such a model comes
+    // host-sized.)
+    const bool frozen = m->bpe.frozen_ok && !c.drop;
     // Two sentences per wave first; the rest (long / non-UTF-8-regular) one
     // per wave from the device-side list.
     BPE_TRY(ws->w_rest.Reserve(nn * 4));
     if (slot >= 0) BPE_TRY(hipEventRecord(ws->tev[2 * slot], st));
-    if (c.drop) {
+    if (frozen) {
+      // (nothing first: the frozen-symbol tier below flags and takes every sentence)
+    } else if (c.drop) {
       // One sentence per wave with the probed pairs masked; the short-slab
       // pass first unless SPM_HIP_BPE_DROPOUT_SHORT=0 (A/B knob).
       static const int kShortKnob = [] {
@@ -1486,7 +1535,7 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
       t.literal = ws->w_bpe_lit.as<uint32_t>();
       t.word_closed = m->bpe.word_closed && m->bpe.lane_ok && kTextKnob != 2 ? 1 : 0;
     }
-    if (!c.drop) {
+    if (!c.drop && !frozen) {
       const uint32_t *fast_list = ws->w_rest.as<uint32_t>(), *fast_count = status + kStBpeRest;
       if (text && !kFastOnly) {
         BPE_TRY(LaunchBpeSplit(t, st));
@@ -1513,6 +1562,25 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
     if (text) {
       BPE_TRY(LaunchBpeText(t, st));
       lit_list = t.literal;
+      lit_count = status + kStBpeLiteral;
+    }
+    if (frozen) {
+      BPE_TRY(ws->w_bpe_lit.Reserve(nn * 4));
+      BpeFrozenLaunch f{};
+      f.t = BpeLineArgsOf(a);
+      f.off = a.off;
+      f.n = n;
+      f.ntok = a.ntok;
+      f.status = status;
+      f.capacity = cap;
+      f.chain = c.out_status;
+      f.ud = m->bpe.ud.as<uint32_t>();
+      f.ud_units = m->bpe.ud_units;
+      f.ud_root = m->bpe.ud_root;
+      f.rest = ws->w_rest.as<uint32_t>();
+      f.literal = ws->w_bpe_lit.as<uint32_t>();
+      BPE_TRY(LaunchBpeFrozen(f, st));
+      lit_list = f.literal;
       lit_count = status + kStBpeLiteral;
     }
     GenBpeArgs g1{a, lit_list, lit_count, 0, ws->w_scratch.as<uint8_t>(), gp.slab,

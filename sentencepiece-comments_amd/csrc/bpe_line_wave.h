@@ -30,6 +30,14 @@
 //   The pair (left, right) is named by the left symbol's first byte and the
 //   byte one past the right symbol's last: symbols only grow, so no name
 //   comes twice in a sentence and the mask is a pure function of it.
+//   kFrozen (bpe_frozen.hip: models with user-defined symbols): the caller has
+//   checked that the sentence's OneCharLen walk is its non-continuation bytes
+//   and has left in S.key[p], for every p < nb, the length of the frozen
+//   symbol that starts at p, kFrozenInside for a byte inside one, else 0.  A
+//   frozen symbol enters the split as one symbol whose `sym` is negative, the
+//   form of a char outside pieces_: no probe ever pairs it (PairLookupFused
+//   returns at once, as MaybeAddNewSymbolPair does), and its id is the piece
+//   lookup of its bytes.  Nothing else differs.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -41,6 +49,7 @@ namespace spm_amd {
 namespace {
 
 constexpr uint32_t kNoSym = 0xFFFFu;  // next: no live symbol starts here; prev: the first symbol
+constexpr uint32_t kFrozenInside = 0xFFFFFFFFu;  // kFrozen, S.key on entry: a byte inside a frozen symbol
 
 // One wave's symbol state, by byte position.
 template <uint32_t kMaxBytes>
@@ -64,7 +73,7 @@ __device__ __forceinline__ uint32_t Uniform(uint32_t v) {
 // (kRightAlign: to [nb - ntok, nb), the batch tiers' slot layout); returns
 // ntok, or kNone when the sentence is not taken.  Wave-uniform result; all 64
 // lanes call it together.
-template <uint32_t kMaxBytes, bool kDrop, bool kRightAlign>
+template <uint32_t kMaxBytes, bool kDrop, bool kRightAlign, bool kFrozen = false>
 __device__ uint32_t BpeEncodeLineWave(const BpeArgs &a, BpeLineSymsT<kMaxBytes> &S, const uint8_t *__restrict__ s,
                                       uint32_t nb, int32_t *__restrict__ out_ids, uint32_t *__restrict__ out_len,
                                       const BpeDropKey &drop) {
@@ -85,14 +94,20 @@ __device__ uint32_t BpeEncodeLineWave(const BpeArgs &a, BpeLineSymsT<kMaxBytes> 
     const uint32_t c = s[p];
     uint32_t cl = OneCharLenB(c);
     if (cl > nb - p) cl = nb - p;
-    const bool start = !cont(c);
-    if (p == 0 && !start) odd = true;
-    if (start) {
-      for (uint32_t j = 1; j < cl; ++j)
-        if (!cont(s[p + j])) odd = true;
-      if (p + cl < nb && cont(s[p + cl])) odd = true;
+    bool start = !cont(c);
+    if constexpr (kFrozen) {  // (the walk is regular: the caller's check)
+      const uint32_t mark = S.key[p];
+      start = start && mark != kFrozenInside;
+      if (mark != 0 && mark != kFrozenInside) cl = mark;
+    } else {
+      if (p == 0 && !start) odd = true;
+      if (start) {
+        for (uint32_t j = 1; j < cl; ++j)
+          if (!cont(s[p + j])) odd = true;
+        if (p + cl < nb && cont(s[p + cl])) odd = true;
+      }
+      S.key[p] = cl;
     }
-    S.key[p] = cl;
     S.next[p] = static_cast<uint16_t>(start ? p + cl : kNoSym);
     S.prev[p] = static_cast<uint16_t>(kNoSym);
   }
@@ -120,7 +135,10 @@ __device__ uint32_t BpeEncodeLineWave(const BpeArgs &a, BpeLineSymsT<kMaxBytes> 
         sym = a.entry_piece[e];
         out = a.entry_out[e];
       }
-      if (a.irregular && sym < 0) bad = true;
+      bool frozen = false;
+      if constexpr (kFrozen) frozen = S.key[p] != 0;  // (a symbol starts here: not kFrozenInside)
+      if (frozen) sym = -1;
+      if (a.irregular && sym < 0 && !frozen) bad = true;
       S.sym[p] = sym >= 0 ? sym : -1 - out;
     }
     S.key[p] = 0;

@@ -224,6 +224,7 @@ struct spm_hip_model {
   // Of the last blocking BPE Encode: flagged sentences by the tier that
   // finished them (pool_mu); their sum is last_stats.general_path.
   uint64_t bpe_word_tier = 0, bpe_wave_tier = 0, bpe_literal = 0;
+  uint64_t bpe_frozen_taken = 0, bpe_frozen_handed = 0;  // the frozen-symbol tier's share of that Encode
   std::atomic<uint32_t> nbest_hyps1{0}, nbest_hyps2{0};  // spm_hip_model_set_nbest_max_hyps
   int device = 0;
 };

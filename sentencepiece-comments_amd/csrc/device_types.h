@@ -83,6 +83,13 @@ struct BpeDevice {
   // splits into independent words (bpe_words.hip).  Set at load from the
   // strings alone; re-tagging pieces never changes it.
   bool word_closed = false;
+  // Models with user-defined symbols (bpe_frozen.hip): 8 words of first-byte
+  // filter, then the double array over the user-defined pieces alone.
+  // frozen_ok: every such piece is whole chars without a NUL byte, so the
+  // frozen-symbol tier takes the model (SPM_HIP_BPE_FROZEN=0: never).
+  DevBuf ud;
+  uint32_t ud_units = 0, ud_root = 0;
+  bool frozen_ok = false;
 };
 
 }  // namespace spm_amd

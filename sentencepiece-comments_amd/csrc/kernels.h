@@ -33,6 +33,9 @@ enum : int {
   kStBpeWordDone = 13, // sentences the word tier finished
   kStBpeWaveDone = 14, // sentences the wave tier finished
   kStBpeWordRest = 15, // word tier: sentences its short-state launch left to the full one
+  // BPE frozen-symbol tier (bpe_frozen.hip; the text tiers do not run then):
+  kStBpeFrozenDone = 10, // sentences the frozen tier finished
+  kStBpeFrozenRest = 11, // sentences its short-state launch left to the full one
   kStWords = 16
 };
 
@@ -588,6 +591,30 @@ hipError_t LaunchBpeText(const BpeTextLaunch &d, hipStream_t st);
 // sentences of `rest` over 64 bytes are flagged (as bpe_fast_kernel flags
 // them, but a block at a time), the others listed in fast_list for it.
 hipError_t LaunchBpeSplit(const BpeTextLaunch &d, hipStream_t st);
+
+// BPE frozen-symbol tier (bpe_frozen.hip), for models with user-defined
+// symbols, in place of the first kernels and the text tiers: every sentence
+// is flagged (status[kStFlagged] = n), one sentence per wave, <= kBpeLineMaxBytes
+// bytes, the short ones first (kBpeDropShortBytes, the others through `rest`,
+// status[kStBpeFrozenRest]).  ud: 8 words of first-byte filter (bit c: some
+// user-defined piece starts with byte c), then the ud_units units of the
+// double array over the user-defined pieces, root base ud_root.  What the tier
+// does not finish (status[kStBpeFrozenDone] counts what it does) is listed in
+// `literal` (status[kStBpeLiteral] entries) for bpe_general_kernel; both lists
+// hold up to n entries.  t: the model's tables as in BpeDropoutLaunch.
+struct BpeFrozenLaunch {
+  BpeLineArgs t;
+  const uint64_t *off;
+  uint64_t n;
+  uint32_t *ntok;
+  uint32_t *status;          // kStWords
+  uint64_t capacity;         // caller's bound on off[n]
+  const uint32_t *chain;     // asynchronous chain status (nullable)
+  const uint32_t *ud;
+  uint32_t ud_units, ud_root;
+  uint32_t *rest, *literal;
+};
+hipError_t LaunchBpeFrozen(const BpeFrozenLaunch &d, hipStream_t st);
 
 // Resident service kernel for small calls (coop_service_kernel): one block
 // polls `box` in pinned coherent host memory; the host writes `call` and

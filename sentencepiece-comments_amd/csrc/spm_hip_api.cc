@@ -512,8 +512,8 @@ int LongestSentence(const uint64_t *d_off, uint64_t n, hipStream_t st, uint32_t 
 // The tier counts and kernel times of a blocking call that has been waited
 // for: `flagged` sentences left the fast tier, or all n when the call ran
 // host-sized.  Publishes the call's stats.
-// bpe_done (BPE Encode, else nullptr): the flagged sentences the word and the
-// wave tier finished; published with the stats under one lock, so that
+// bpe_done (BPE Encode, else nullptr): the flagged sentences the word, the
+// wave and the frozen-symbol tier finished; published with the stats under one lock, so that
 // their sum with the literal kernel's share is this call's general_path.
 int PublishTierStats(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n, bool host_sized, uint32_t flagged,
                      const uint64_t *bpe_done = nullptr) {
@@ -534,6 +534,8 @@ int PublishTierStats(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n,
   m->bpe_word_tier = host_sized ? 0 : bpe_done[0];
   m->bpe_wave_tier = host_sized ? 0 : bpe_done[1];
   m->bpe_literal = ws->stats.general_path - m->bpe_word_tier - m->bpe_wave_tier;
+  m->bpe_frozen_taken = host_sized ? 0 : bpe_done[2];
+  m->bpe_frozen_handed = m->bpe.frozen_ok && !host_sized ? n - bpe_done[2] : 0;
   return SPM_OK;
 }
 
@@ -989,7 +991,14 @@ bool NeedsHostSized(const spm_hip_model *m) {
   if (WordCharModel(m)) return false;
   if (m->force_general) return true;
   if (m->model_type == spm_amd::kUnigram) return m->kernel == spm_amd::UnigramKernel::kGeneralOnly;
-  return m->bpe.has_user_defined;
+  // User-defined symbols: the frozen-symbol tier takes the model, or the
+  // literal kernel runs over every sentence.
+  return m->bpe.has_user_defined && !m->bpe.frozen_ok;
+}
+
+// The one-launch line path keeps refusing BPE models with user-defined symbols.
+bool BpeUserDefined(const spm_hip_model *m) {
+  return m->model_type == spm_amd::kBpe && m->bpe.has_user_defined;
 }
 
 // Enqueues one encode (no synchronization unless c.host_sized).
@@ -1012,7 +1021,9 @@ int EncodeBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t
   uint64_t total = 0;
   int rc = BatchBytes(ws, d_off, n, st, &total);
   if (rc != SPM_OK) return rc;
-  spm_amd::EncodeCall c{d_bytes, d_off, n, total, d_ids, d_len, d_tok, nullptr, st, NeedsHostSized(m), 0, drop};
+  // (BPE-dropout of a model with user-defined symbols: bpe_general_kernel<true> over every sentence.)
+  spm_amd::EncodeCall c{d_bytes, d_off, n, total, d_ids, d_len, d_tok, nullptr, st,
+                        NeedsHostSized(m) || (drop && BpeUserDefined(m)), 0, drop};
   if (c.host_sized && (rc = LongestSentence(d_off, n, st, &c.max_nb)) != SPM_OK) return rc;
   ws->stats = spm_hip_encode_stats{};
   if ((rc = EncodeEnqueue(m, ws, c)) != SPM_OK) return rc;
@@ -1021,7 +1032,11 @@ int EncodeBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t
   uint32_t flagged = ws->pinned[spm_amd::kStFlagged], err = ws->pinned[spm_amd::kStError];
   // BPE Encode: the flagged sentences the word and the wave tier finished.
   const bool bpe_tiers = m->model_type == spm_amd::kBpe && !drop;
-  const uint64_t bpe_done[2] = {ws->pinned[spm_amd::kStBpeWordDone], ws->pinned[spm_amd::kStBpeWaveDone]};
+  // ... and the frozen-symbol tier (models with user-defined symbols; its
+  // status word is the text tiers' kStBpeWaveList, which do not run then).
+  const bool frozen = bpe_tiers && m->bpe.frozen_ok && !c.host_sized;
+  const uint64_t bpe_done[3] = {ws->pinned[spm_amd::kStBpeWordDone], ws->pinned[spm_amd::kStBpeWaveDone],
+                                frozen ? ws->pinned[spm_amd::kStBpeFrozenDone] : 0};
   if (err && !c.host_sized) {
     c.host_sized = true;
     rc = LongestSentence(d_off, n, st, &c.max_nb);
@@ -1487,7 +1502,7 @@ void spm_hip_model_free(spm_hip_model *m) {
                  static_cast<unsigned long long>(m->bpe_line_skipped.load()));
   for (spm_amd::DevBuf *b : {&m->d_units, &m->d_uvs, &m->d_piece_tab, &m->d_values, &m->d_scores,
                              &m->bpe.pair_keys, &m->bpe.pair_vals, &m->bpe.pair_ent, &m->bpe.rank_piece, &m->bpe.entry_piece,
-                             &m->bpe.entry_out, &m->bpe.piece_kind, &m->bpe.piece_out,
+                             &m->bpe.entry_out, &m->bpe.piece_kind, &m->bpe.piece_out, &m->bpe.ud,
                              &m->d_wc_tab, &m->d_wc_keys, &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_byte_ids, &m->d_types_kind, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes})
     b->Release();
   for (auto &kv : m->by_stream) kv.second->Release();
@@ -2993,7 +3008,7 @@ int spm_hip_encode_raw_small_host(spm_hip_model *m, const uint8_t *raw, const ui
   // BPE model with USER_DEFINED pieces.
   const bool bpe = m->model_type == spm_amd::kBpe;
   if (n == 0 || n > spm_amd::kCoopSmallMax || raw_off[0] != 0 || raw_off[n] > kSmallMaxBytes / 8 ||
-      m->byte_fallback || (m->model_type != spm_amd::kUnigram && !bpe) || NeedsHostSized(m) ||
+      m->byte_fallback || (m->model_type != spm_amd::kUnigram && !bpe) || NeedsHostSized(m) || BpeUserDefined(m) ||
       (!bpe && (!m->d_uvs.ptr || m->max_piece_bytes > 56)))
     return SPM_UNIMPLEMENTED;
   for (uint64_t i = 0; i < n; ++i)
@@ -3062,7 +3077,7 @@ int spm_hip_encode_batch_host(spm_hip_model *m, const uint8_t *bytes, const uint
   // pinned down to batches of one sentence.
   uint64_t bpe_refused = 0;
   if (n >= 1 && n <= spm_amd::kCoopSmallMax && total <= kSmallMaxBytes && m->model_type == spm_amd::kBpe &&
-      !NeedsHostSized(m) && BpeSmallHostOn() && BpeLineTry(m)) {
+      !NeedsHostSized(m) && !BpeUserDefined(m) && BpeSmallHostOn() && BpeLineTry(m)) {
     bool done = false;
     const int rc = EncodeHostBpe(m, ws.get(), bytes, off, n, ids, len, tok, st, &done);
     if (rc != SPM_OK) return rc;
@@ -3522,6 +3537,14 @@ int spm_hip_bpe_tier_last_stats(const spm_hip_model *m, uint64_t *word_tier, uin
   if (word_tier) *word_tier = m->bpe_word_tier;
   if (wave_tier) *wave_tier = m->bpe_wave_tier;
   if (literal) *literal = m->bpe_literal;
+  return SPM_OK;
+}
+
+int spm_hip_bpe_frozen_last_stats(const spm_hip_model *m, uint64_t *taken, uint64_t *handed_on) {
+  if (!m) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  std::lock_guard<std::mutex> lk(const_cast<spm_hip_model *>(m)->pool_mu);
+  if (taken) *taken = m->bpe_frozen_taken;
+  if (handed_on) *handed_on = m->bpe_frozen_handed;
   return SPM_OK;
 }
 

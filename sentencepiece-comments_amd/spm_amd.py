@@ -54,6 +54,7 @@ EXPORTED = [
     "spm_hip_sample_encode_and_score_batch_host", "spm_hip_sample_seed",
     "spm_hip_nbest_encode_batch", "spm_hip_nbest_encode_batch_host", "spm_hip_model_set_nbest_max_hyps",
     "spm_hip_nbest_last_stats", "spm_hip_model_bpe_word_closed", "spm_hip_bpe_tier_last_stats",
+    "spm_hip_bpe_frozen_last_stats",
     "spm_hip_model_set_piece_types", "spm_hip_model_get_piece_types", "spm_hip_model_set_vocabulary",
     "spm_hip_model_reset_vocabulary", "spm_hip_count_ids", "spm_hip_count_ids_host",
     "spm_hip_model_byte_fallback", "spm_hip_finalize_ids_bytes", "spm_hip_finalize_ids_bytes_async",
@@ -245,6 +246,7 @@ def lib():
         L.spm_hip_nbest_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_model_bpe_word_closed.argtypes = [P, ctypes.POINTER(ctypes.c_int)]
         L.spm_hip_bpe_tier_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64), ctypes.POINTER(U64)]
+        L.spm_hip_bpe_frozen_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_device_peak_reset.restype = None
         L.spm_hip_decode_batch.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, ctypes.POINTER(U64), P]
         L.spm_hip_decode_batch_async.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, P, P]
@@ -868,6 +870,14 @@ class DeviceModel:
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(self._L.spm_hip_bpe_tier_last_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
+
+    def bpe_frozen_stats(self):
+        """(taken, handed_on): of the last blocking Encode of a BPE model with
+        user-defined symbols, the sentences the frozen-symbol tier finished
+        and the ones it left to the literal kernel."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._L.spm_hip_bpe_frozen_last_stats(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def encode_normalized(self, sentences):
         buf, off = to_csr(sentences)
