@@ -1160,6 +1160,78 @@ int spm_hip_fit_ids_host(const int32_t *ids, const uint64_t *offsets, uint64_t n
                          int32_t pad_id, uint32_t flags, uint64_t rows_capacity, int32_t *out, int32_t *seq,
                          int32_t *pos, int32_t *row_lengths, uint64_t *place, uint64_t *stats);
 
+/* Text rows: the text around a corpus run, on the device.  spm_encode reads
+ * lines and prints one row of ids or pieces per line; these three calls do
+ * both ends without a host loop over lines, ids or pieces.  No reference
+ * counterpart (the reference's spm_encode uses std::getline and a string
+ * join per line).
+ *
+ * Split: d_text[nbytes] -> the sentence CSR every batch entry takes.
+ * std::getline semantics: a line ends at '\n'; a '\r' before it is kept; a
+ * final fragment without '\n' is a line; a buffer that ends in '\n' gives no
+ * extra empty line; nbytes == 0 gives zero lines; every other byte (NUL,
+ * malformed UTF-8) passes through.  Outputs: d_out_bytes, the lines' bytes
+ * without the separators (it must hold nbytes bytes; counts[1] of them are
+ * written); d_out_offsets[line_capacity + 1], line i = bytes [offsets[i],
+ * offsets[i+1]); nullable d_counts[2] (uint64: lines n, bytes of the lines).
+ * With n > line_capacity the offsets [0, line_capacity] and all the bytes are
+ * written, nothing past either buffer, d_counts holds the need and
+ * *d_status := SPM_RESOURCE_EXHAUSTED.  d_text may have any alignment.
+ *
+ * Id rows: a final id CSR (d_ids / d_offsets[n+1]; the offsets index d_ids
+ * and need not start at 0) -> the text of spm_encode --output_format=id: each
+ * row its ids in decimal joined by one ' ', then '\n'; an empty row is a lone
+ * '\n'.  Piece rows: the records and the normalized text of
+ * spm_hip_encode_spt (d_pieces / d_piece_offsets[n+1], d_norm /
+ * d_norm_offsets[n+1]) -> the text of --output_format=piece: the piece of a
+ * record is normalized[norm_begin, norm_end) of its sentence, or IdToPiece(id)
+ * where that span is empty (the bos / eos pieces of the extra options, BYTE
+ * pieces); pieces joined by ' ', then '\n'.  Both write d_out_bytes (capacity
+ * out_capacity bytes) and d_row_offsets[n+1], row i = bytes [row_offsets[i],
+ * row_offsets[i+1]), so a caller cuts rows without scanning.  The offsets are
+ * always complete and row_offsets[n] is the needed size; no byte at or past
+ * out_capacity is written, and if the text is longer *d_status :=
+ * SPM_RESOURCE_EXHAUSTED.  An id below 0 (id rows), an empty span whose id is
+ * outside [0, piece_size) or a span that leaves its sentence (piece rows)
+ * gives *d_status := SPM_OUT_OF_RANGE and unspecified text.  Sizing: 11 bytes
+ * per id plus one per row; piece rows: the normalized bytes + one byte per
+ * record and per row + max_piece_bytes for every record with an empty span.
+ * 256 consecutive pieces must stay under 4 GiB together.
+ *
+ * All three are pure stream calls in the sense of the _async entries (status
+ * word contract of spm_hip_encode_batch_async: nothing is read or written
+ * once *d_status is non-zero, first error wins).  They work in d_scratch:
+ * SPM_HIP_TEXT_ROWS_SCRATCH_BYTES of device memory, 8-byte aligned, contents
+ * undefined before and after, not shared by calls that may overlap.  Split
+ * and id rows take no model handle; piece rows reads the model's piece
+ * strings (a device table uploaded when the model is loaded) and is SPM_FAILED_PRECONDITION
+ * on a host-only handle.  SPM_INVALID_ARGUMENT: a null d_status, d_scratch,
+ * offsets or output pointer; n > INT32_MAX.
+ *
+ * The _host forms take host pointers, run the same per-row rule in a plain
+ * loop on the calling thread and never touch the GPU; they return the status
+ * the device calls leave in *d_status and, on SPM_OUT_OF_RANGE, write nothing.
+ * spm_hip_format_piece_rows_host works on a host-only handle. */
+#define SPM_HIP_TEXT_ROWS_SCRATCH_BYTES 16384
+int spm_hip_split_lines(const uint8_t *d_text, uint64_t nbytes, uint8_t *d_out_bytes, uint64_t *d_out_offsets,
+                        uint64_t line_capacity, uint64_t *d_counts, uint32_t *d_status, void *d_scratch,
+                        void *stream);
+int spm_hip_split_lines_host(const uint8_t *text, uint64_t nbytes, uint8_t *out_bytes, uint64_t *out_offsets,
+                             uint64_t line_capacity, uint64_t *counts);
+int spm_hip_format_id_rows(const int32_t *d_ids, const uint64_t *d_offsets, uint64_t n, uint8_t *d_out_bytes,
+                           uint64_t out_capacity, uint64_t *d_row_offsets, uint32_t *d_status, void *d_scratch,
+                           void *stream);
+int spm_hip_format_id_rows_host(const int32_t *ids, const uint64_t *offsets, uint64_t n, uint8_t *out_bytes,
+                                uint64_t out_capacity, uint64_t *row_offsets);
+int spm_hip_format_piece_rows(spm_hip_model *model, const spm_hip_piece *d_pieces,
+                              const uint64_t *d_piece_offsets, uint64_t n, const uint8_t *d_norm,
+                              const uint64_t *d_norm_offsets, uint8_t *d_out_bytes, uint64_t out_capacity,
+                              uint64_t *d_row_offsets, uint32_t *d_status, void *d_scratch, void *stream);
+int spm_hip_format_piece_rows_host(spm_hip_model *model, const spm_hip_piece *pieces,
+                                   const uint64_t *piece_offsets, uint64_t n, const uint8_t *norm,
+                                   const uint64_t *norm_offsets, uint8_t *out_bytes, uint64_t out_capacity,
+                                   uint64_t *row_offsets);
+
 /* Device memory this library holds in the calling process (every block it
  * allocates: models' workspaces, E-step piece sets, trainer corpus and
  * scratch): live bytes now and the high-water mark since the last reset.

@@ -214,6 +214,12 @@ struct spm_hip_model {
   // Decode table (decode.h), built at load; the device copy unless host_only.
   spm_amd::DecodeTable decode;
   spm_amd::DevBuf d_dec_meta, d_dec_off, d_dec_bytes;
+  // Piece strings (text_rows.h): IdToPiece(i) = pstr_bytes[pstr_off[i], pstr_off[i + 1]).  Built at
+  // load, with the device copy unless host_only.
+  std::vector<uint32_t> pstr_off;
+  std::vector<uint8_t> pstr_bytes;
+  spm_amd::DevBuf d_pstr_off, d_pstr_bytes;
+  std::atomic<bool> pstr_host_ready{false}, pstr_dev_ready{false};
   // Workspaces (under pool_mu): one per caller stream, a pool for the host API.
   std::mutex pool_mu;
   std::unordered_map<hipStream_t, std::unique_ptr<spm_amd::EncodeWorkspace>> by_stream;

@@ -7,6 +7,7 @@
 #include "scratch_cache.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -380,7 +381,8 @@ Status SentencePieceProcessor::SampleEncode(const std::string &input, int nbest_
 namespace {
 enum {
   kIn, kInOff, kNorm, kNormOff, kIds, kLen, kTok, kOut, kOutOff, kSmallBlockSlot, kCounts,
-  kDenseIds, kDenseAux0, kDenseAux1, kDenseStats, kDenseScratch, kDenseRowLengths, kDensePlace
+  kDenseIds, kDenseAux0, kDenseAux1, kDenseStats, kDenseScratch, kDenseRowLengths, kDensePlace,
+  kTrText, kTrLines, kTrOff, kTrCtl, kTrScratch, kTrRows, kTrRowOff, kTrAlign, kTrPieces, kTrPieceOff
 };
 }  // namespace
 
@@ -529,6 +531,22 @@ Status SentencePieceProcessor::DeviceEncode(const std::vector<std::string> &inpu
   uint64_t total = 0;
   Status st = DeviceNormalize(inputs, &d_norm, &d_norm_off, &total);
   if (!st.ok()) return st;
+  return EncodeNormalized(d_norm, d_norm_off, total, n, sample, b);
+}
+
+Status SentencePieceProcessor::DeviceEncodeCsr(const uint8_t *d_in, const uint64_t *d_in_off, uint64_t n,
+                                               const SampleSpec *sample, DeviceBatch *b) const {
+  uint8_t *d_norm = nullptr;
+  uint64_t *d_norm_off = nullptr;
+  uint64_t total = 0;
+  Status st = DeviceNormalizeCsr(d_in, d_in_off, n, &d_norm, &d_norm_off, &total);
+  if (!st.ok()) return st;
+  return EncodeNormalized(d_norm, d_norm_off, total, n, sample, b);
+}
+
+Status SentencePieceProcessor::EncodeNormalized(uint8_t *d_norm, uint64_t *d_norm_off, uint64_t total, uint64_t n,
+                                                const SampleSpec *sample, DeviceBatch *b) const {
+  Status st;
   uint64_t *d_tok = static_cast<uint64_t *>(dev_.Get(kTok, (n + 1) * 8));
   int32_t *d_ids = static_cast<int32_t *>(dev_.Get(kIds, std::max<uint64_t>(total, 1) * 4));
   uint32_t *d_len = static_cast<uint32_t *>(dev_.Get(kLen, std::max<uint64_t>(total, 1) * 4));
@@ -558,12 +576,19 @@ Status SentencePieceProcessor::DeviceNormalize(const std::vector<std::string> &i
   auto fail_hip = [](hipError_t e) { return Err(SPM_INTERNAL, hipGetErrorString(e)); };
   uint8_t *d_in = static_cast<uint8_t *>(dev_.Get(kIn, in_off[n]));
   uint64_t *d_in_off = static_cast<uint64_t *>(dev_.Get(kInOff, (n + 1) * 8));
-  uint64_t *d_norm_off = static_cast<uint64_t *>(dev_.Get(kNormOff, (n + 1) * 8));
-  if (!d_in || !d_in_off || !d_norm_off) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+  if (!d_in || !d_in_off) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
   hipError_t he;
   if ((he = hipMemcpy(d_in, in_bytes.data(), in_off[n], hipMemcpyHostToDevice)) != hipSuccess ||
       (he = hipMemcpy(d_in_off, in_off.data(), (n + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess)
     return fail_hip(he);
+  return DeviceNormalizeCsr(d_in, d_in_off, n, d_norm_out, d_norm_off_out, total_out);
+}
+
+Status SentencePieceProcessor::DeviceNormalizeCsr(const uint8_t *d_in, const uint64_t *d_in_off, uint64_t n,
+                                                  uint8_t **d_norm_out, uint64_t **d_norm_off_out,
+                                                  uint64_t *total_out) const {
+  uint64_t *d_norm_off = static_cast<uint64_t *>(dev_.Get(kNormOff, (n + 1) * 8));
+  if (!d_norm_off) return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
   uint64_t total = 0;
   uint64_t ncap = dev_.cap[kNorm];
   uint8_t *d_norm = static_cast<uint8_t *>(dev_.Get(kNorm, std::max<uint64_t>(ncap, 1)));
@@ -676,6 +701,125 @@ Status SentencePieceProcessor::RunBatch(const std::vector<std::string> &inputs, 
     if (pieces)
       for (auto &p : spt) (*pieces)[i].push_back(std::move(p.first));
   }
+  return Status::Ok();
+}
+
+void SentencePieceProcessor::TextRowsTimes(double ms[3]) const {
+  for (int k = 0; k < 3; ++k) ms[k] = text_ms_[k];
+}
+
+bool SentencePieceProcessor::TextRowsSupported() const {
+  const int t = proto_.trainer_spec.model_type;
+  return status_.ok() && !host_only_ && t != kWord && t != kChar;
+}
+
+Status SentencePieceProcessor::EncodeTextRows(const char *text, size_t nbytes, TextRowsFormat format,
+                                              std::string *out) const {
+  if (!status_.ok()) return status_;
+  if (!out || (nbytes && !text)) return Err(SPM_INTERNAL, "null argument");
+  if (!TextRowsSupported()) return Err(SPM_UNIMPLEMENTED, "text rows: take the rows from EncodeBatch for this processor");
+  out->clear();
+  if (nbytes == 0) return Status::Ok();
+  auto fail_hip = [](hipError_t e) { return Err(SPM_INTERNAL, hipGetErrorString(e)); };
+  auto oom = []() { return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed"); };
+  hipError_t he;
+  uint8_t *d_text = static_cast<uint8_t *>(dev_.Get(kTrText, nbytes));
+  uint8_t *d_lines = static_cast<uint8_t *>(dev_.Get(kTrLines, nbytes));
+  uint64_t *d_ctl = static_cast<uint64_t *>(dev_.Get(kTrCtl, 32));  // status word, counts[2]
+  void *d_scratch = dev_.Get(kTrScratch, SPM_HIP_TEXT_ROWS_SCRATCH_BYTES);
+  if (!d_text || !d_lines || !d_ctl || !d_scratch) return oom();
+  uint32_t *d_status = reinterpret_cast<uint32_t *>(d_ctl);
+  using Clock = std::chrono::steady_clock;
+  auto ms_since = [](Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); };
+  Clock::time_point t0 = Clock::now();
+  if ((he = hipMemcpy(d_text, text, nbytes, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(he);
+  text_ms_[0] += ms_since(t0);
+  t0 = Clock::now();
+  // Split.  The line capacity is a guess from the last call's line length; a
+  // buffer with more lines reports its count and runs once more.
+  uint64_t ctl[3] = {0, 0, 0};
+  uint64_t *d_off = nullptr;
+  for (uint64_t cap = nbytes / text_line_div_ + 16;; cap = ctl[1]) {
+    d_off = static_cast<uint64_t *>(dev_.Get(kTrOff, (cap + 1) * 8));
+    if (!d_off) return oom();
+    if ((he = hipMemset(d_ctl, 0, 32)) != hipSuccess) return fail_hip(he);
+    Status st = FromC(spm_hip_split_lines(d_text, nbytes, d_lines, d_off, cap, d_ctl + 1, d_status, d_scratch, nullptr));
+    if (!st.ok()) return st;
+    if ((he = hipMemcpy(ctl, d_ctl, 24, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(he);
+    if (static_cast<uint32_t>(ctl[0]) == SPM_OK) break;
+    if (static_cast<uint32_t>(ctl[0]) != SPM_RESOURCE_EXHAUSTED || ctl[1] <= cap) return Err(SPM_INTERNAL, "split lines");
+  }
+  const uint64_t n = ctl[1];
+  if (n > 0x7FFFFFFFull) return Err(SPM_OUT_OF_RANGE, "too many lines in one buffer");
+  text_line_div_ = std::max<uint64_t>(1, std::min<uint64_t>(64, nbytes / (n + n / 8 + 1)));
+  uint64_t *d_row_off = static_cast<uint64_t *>(dev_.Get(kTrRowOff, (n + 1) * 8));
+  if (!d_row_off) return oom();
+  uint8_t *d_rows = nullptr;
+  uint64_t need = 0;
+  uint32_t status = 0;
+  if (format == kTextRowsId) {
+    DeviceBatch b;
+    Status st = DeviceEncodeCsr(d_lines, d_off, n, nullptr, &b);
+    if (!st.ok()) return st;
+    int32_t *d_ids = nullptr;
+    uint64_t *d_ids_off = nullptr;
+    uint64_t fin = 0;
+    st = DeviceFinalize(b, n, &d_ids, &d_ids_off, &fin);
+    if (!st.ok()) return st;
+    const uint64_t cap = 11 * fin + n;  // always enough
+    d_rows = static_cast<uint8_t *>(dev_.Get(kTrRows, cap));
+    if (!d_rows) return oom();
+    st = FromC(spm_hip_format_id_rows(d_ids, d_ids_off, n, d_rows, cap, d_row_off, d_status, d_scratch, nullptr));
+    if (!st.ok()) return st;
+  } else {
+    // Encode(SentencePieceText) on the device gives the records; sized by
+    // its own report where the first guess was short.
+    uint64_t ncap = std::max<uint64_t>(dev_.cap[kNorm], nbytes + nbytes / 2 + 3 * n + 16), tn = 0, tp = 0;
+    uint64_t *d_norm_off = static_cast<uint64_t *>(dev_.Get(kNormOff, (n + 1) * 8));
+    uint64_t *d_poff = static_cast<uint64_t *>(dev_.Get(kTrPieceOff, (n + 1) * 8));
+    uint8_t *d_norm = nullptr;
+    spm_hip_piece *d_pieces = nullptr;
+    if (!d_norm_off || !d_poff) return oom();
+    for (int round = 0;; ++round) {
+      const uint64_t pcap = ncap + 2 * n;
+      d_norm = static_cast<uint8_t *>(dev_.Get(kNorm, ncap));
+      uint32_t *d_align = static_cast<uint32_t *>(dev_.Get(kTrAlign, (ncap + n) * 4));
+      d_pieces = static_cast<spm_hip_piece *>(dev_.Get(kTrPieces, pcap * sizeof(spm_hip_piece)));
+      if (!d_norm || !d_align || !d_pieces) return oom();
+      const int rc = spm_hip_encode_spt(model_, extra_str_.c_str(), d_lines, d_off, n, d_norm, ncap, d_norm_off,
+                                        d_align, d_pieces, pcap, d_poff, &tn, &tp, nullptr);
+      if (rc == SPM_RESOURCE_EXHAUSTED && round == 0) {
+        ncap = std::max(ncap, std::max(tn, tp));
+        continue;
+      }
+      Status st = FromC(rc);
+      if (!st.ok()) return st;
+      break;
+    }
+    // Enough unless many records take their piece from the table (bos / eos,
+    // BYTE pieces); a text that does not fit reports its size in row_off[n].
+    for (uint64_t cap = tn + 8 * tp + n;; cap = need) {
+      d_rows = static_cast<uint8_t *>(dev_.Get(kTrRows, cap));
+      if (!d_rows) return oom();
+      Status st = FromC(spm_hip_format_piece_rows(model_, d_pieces, d_poff, n, d_norm, d_norm_off, d_rows, cap,
+                                                  d_row_off, d_status, d_scratch, nullptr));
+      if (!st.ok()) return st;
+      if ((he = hipMemcpy(&status, d_status, 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+          (he = hipMemcpy(&need, d_row_off + n, 8, hipMemcpyDeviceToHost)) != hipSuccess)
+        return fail_hip(he);
+      if (status != SPM_RESOURCE_EXHAUSTED || need <= cap) break;
+      if ((he = hipMemset(d_status, 0, 4)) != hipSuccess) return fail_hip(he);
+    }
+  }
+  if ((he = hipMemcpy(&status, d_status, 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (he = hipMemcpy(&need, d_row_off + n, 8, hipMemcpyDeviceToHost)) != hipSuccess)
+    return fail_hip(he);
+  if (status != SPM_OK) return Err(static_cast<int>(status), "text rows: formatting failed");
+  text_ms_[1] += ms_since(t0);
+  t0 = Clock::now();
+  out->resize(need);
+  if (need && (he = hipMemcpy(&(*out)[0], d_rows, need, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(he);
+  text_ms_[2] += ms_since(t0);
   return Status::Ok();
 }
 

@@ -194,6 +194,23 @@ class SentencePieceProcessor {
   // the counters come back.  Accumulates over calls.
   Status CountPieces(const std::vector<std::string> &inputs, std::vector<uint64_t> *counts) const;
 
+  // A text buffer (lines separated by '\n', std::getline's rules) -> the text
+  // spm_encode prints for it with --output_format=id or piece: one row per
+  // line, ids or pieces joined by ' ', with the options of
+  // SetEncodeExtraOptions.  Split, normalize, encode, epilogue and format all
+  // run on the device (spm_hip_split_lines, spm_hip_format_id_rows,
+  // spm_hip_format_piece_rows); one upload, a few word-sized read-backs for
+  // sizes, one copy back of the text.  SPM_UNIMPLEMENTED where the rows must
+  // come from EncodeBatch instead (TextRowsSupported() is false): host-only
+  // processors, and WORD / CHAR models, whose host epilogue fails a line
+  // that holds a CONTROL piece's spelling.
+  enum TextRowsFormat { kTextRowsId, kTextRowsPiece };
+  bool TextRowsSupported() const;
+  Status EncodeTextRows(const char *text, size_t nbytes, TextRowsFormat format, std::string *out) const;
+  // Host wall time of all EncodeTextRows calls so far, in ms: the upload of the text, the device
+  // work with its size read-backs, the copy back of the rows.
+  void TextRowsTimes(double ms[3]) const;
+
   // Decode (sentencepiece_processor.cc:341-370, :670-733).  One piece of
   // SentencePieceText: surface = text[begin, end).
   struct DecodedPiece {
@@ -293,6 +310,15 @@ class SentencePieceProcessor {
   Status DeviceNormalize(const std::vector<std::string> &inputs, uint8_t **d_norm, uint64_t **d_norm_off,
                          uint64_t *total) const;
   Status DeviceFinalize(const DeviceBatch &b, uint64_t n, int32_t **d_out, uint64_t **d_out_off, uint64_t *fin) const;
+  // The same from a raw sentence CSR that is on the device already.
+  Status DeviceEncodeCsr(const uint8_t *d_in, const uint64_t *d_in_off, uint64_t n, const SampleSpec *sample,
+                         DeviceBatch *b) const;
+  Status DeviceNormalizeCsr(const uint8_t *d_in, const uint64_t *d_in_off, uint64_t n, uint8_t **d_norm,
+                            uint64_t **d_norm_off, uint64_t *total) const;
+  Status EncodeNormalized(uint8_t *d_norm, uint64_t *d_norm_off, uint64_t total, uint64_t n,
+                          const SampleSpec *sample, DeviceBatch *b) const;
+  mutable uint64_t text_line_div_ = 16;
+  mutable double text_ms_[3] = {0, 0, 0};  // EncodeTextRows: line capacity guess = bytes / this
   // EncodeDense / SampleEncodeDense.
   Status RunDense(const std::vector<std::string> &inputs, const SampleSpec *sample, const DenseOptions &options,
                   DenseBatch *out, std::vector<int32_t> *host_ids) const;
@@ -304,8 +330,8 @@ class SentencePieceProcessor {
                       uint64_t count, std::vector<std::pair<std::string, int>> *out) const;
   // Grow-only device staging for EncodeBatch (raw lines → normalized → ids).
   struct Staging {
-    void *ptr[18] = {};
-    size_t cap[18] = {};
+    void *ptr[28] = {};
+    size_t cap[28] = {};
     void *Get(int k, size_t bytes);
     ~Staging();
   };

@@ -27,10 +27,23 @@
 // one output line per input line, pieces / ids joined by " ".  Lines are
 // read with std::getline semantics (a trailing '\r' is kept,
 // filesystem.cc:42-44).
+//
+// For --output_format=id and piece the text around the encode is built on the
+// device as well (SentencePieceProcessor::EncodeTextRows): the input is read in
+// byte chunks that end at a newline, a chunk is split into lines, normalized,
+// encoded, run through the epilogue and printed as rows on the device, and one
+// write puts the rows out.  The host path above stays for a chunk of at most
+// 16 lines and for --batch_lines <= 16 (the small-call paths), for the sample
+// and n-best formats, --generate_vocabulary and processors without text rows
+// (WORD / CHAR models); SPM_HIP_TEXT_ROWS=0 restores it everywhere.
+// SPM_HIP_TEXT_ROWS_CHUNK (bytes, a test knob) sets the chunk size;
+// SPM_HIP_TEXT_ROWS_TIMES=1 prints where the wall time went to stderr.
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <string>
@@ -162,6 +175,7 @@ int main(int argc, char **argv) {
         "\": only piece, id, sample_piece, sample_id, nbest_piece and nbest_id are implemented by the device "
         "engine");
 
+  const std::chrono::steady_clock::time_point t_main = std::chrono::steady_clock::now();
   spm_amd::SentencePieceProcessor sp;
   auto st = sp.Load(f.model);
   if (!st.ok()) Die(st.message);
@@ -173,6 +187,8 @@ int main(int argc, char **argv) {
     if (!st.ok()) Die(st.message);
   }
 
+  const double load_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_main).count();
   std::ofstream ofs;
   std::ostream *out = &std::cout;
   if (!f.output.empty()) {
@@ -245,6 +261,40 @@ int main(int argc, char **argv) {
     }
     batch.clear();
   };
+  constexpr long kSmallLines = 16;  // kCoopSmallMax: flushes up to this size keep the small-call paths
+  const char *tr_env = std::getenv("SPM_HIP_TEXT_ROWS");
+  const bool text_rows = !(tr_env && std::string(tr_env) == "0") && !f.generate_vocabulary && !sample && !nbest &&
+                         f.batch_lines > kSmallLines && sp.TextRowsSupported();
+  size_t chunk_bytes = size_t{64} << 20;
+  if (const char *e = std::getenv("SPM_HIP_TEXT_ROWS_CHUNK")) chunk_bytes = std::max(1L, std::atol(e));
+  std::string chunk, rows;
+  using Clock = std::chrono::steady_clock;
+  auto ms_since = [](Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); };
+  double read_ms = 0, write_ms = 0;
+  // One chunk of whole lines (the last may lack its '\n' at the end of a
+  // file): through the device, or line by line into the host path.
+  auto run_chunk = [&](const char *p, size_t len) {
+    long lines = 0;
+    for (const char *q = p, *e = p + len; q < e && lines <= kSmallLines; ++lines) {
+      const void *nl = std::memchr(q, '\n', e - q);
+      q = nl ? static_cast<const char *>(nl) + 1 : e;
+    }
+    if (lines <= kSmallLines) {
+      for (const char *q = p, *e = p + len; q < e;) {
+        const void *nl = std::memchr(q, '\n', e - q);
+        const char *stop = nl ? static_cast<const char *>(nl) : e;
+        batch.emplace_back(q, stop);
+        q = nl ? stop + 1 : e;
+      }
+      flush();
+      return;
+    }
+    auto s = sp.EncodeTextRows(p, len, want_ids ? sp.kTextRowsId : sp.kTextRowsPiece, &rows);
+    if (!s.ok()) Die(s.message);
+    const Clock::time_point t = Clock::now();
+    out->write(rows.data(), rows.size());
+    write_ms += ms_since(t);
+  };
   for (const auto &fn : rest) {
     std::ifstream ifs;
     std::istream *in = &std::cin;
@@ -253,6 +303,28 @@ int main(int argc, char **argv) {
       if (!ifs) Die("\"" + fn + "\": No such file or directory");
       in = &ifs;
     }
+    if (text_rows) {
+      flush();  // nothing is pending; keeps the order if that ever changes
+      chunk.clear();
+      for (;;) {
+        const size_t have = chunk.size();
+        const Clock::time_point t = Clock::now();
+        chunk.resize(have + chunk_bytes);
+        in->read(&chunk[have], chunk_bytes);
+        read_ms += ms_since(t);
+        const size_t got = static_cast<size_t>(in->gcount());
+        chunk.resize(have + got);
+        if (got == 0) break;
+        // Up to the last newline; the rest opens the next chunk.
+        size_t cut = chunk.size();
+        while (cut > have && chunk[cut - 1] != '\n') --cut;
+        if (cut == have) continue;  // no newline in what was read: a longer chunk
+        run_chunk(chunk.data(), cut);
+        chunk.erase(0, cut);
+      }
+      if (!chunk.empty()) run_chunk(chunk.data(), chunk.size());
+      continue;
+    }
     std::string line;
     while (std::getline(*in, line)) {
       batch.push_back(line);
@@ -260,6 +332,15 @@ int main(int argc, char **argv) {
     }
   }
   flush();
+  if (text_rows && std::getenv("SPM_HIP_TEXT_ROWS_TIMES")) {
+    const Clock::time_point t = Clock::now();
+    out->flush();
+    write_ms += ms_since(t);
+    double ms[3];
+    sp.TextRowsTimes(ms);
+    std::fprintf(stderr, "text rows ms: start+load %.1f read %.1f upload %.1f device %.1f copy_back %.1f write %.1f\n",
+                 load_ms, read_ms, ms[0], ms[1], ms[2], write_ms);
+  }
   if (f.generate_vocabulary) {
     std::vector<std::pair<std::string, uint64_t>> vocab;
     for (size_t id = 0; id < counts.size(); ++id)

@@ -20,6 +20,7 @@
 #include "../../include/spm_hip.h"
 #include "bpe_tables.h"
 #include "dense.h"
+#include "text_rows.h"
 #include "device_model.h"
 #include "epilogue.h"
 #include "host_nbest.h"
@@ -1086,6 +1087,8 @@ int EnsureNormTables(spm_hip_model *m) {
 // (sentencepiece_processor.cc:670-716).  Decode(ids) maps an id to its piece
 // and the piece back to an id (PieceToId: reserved pieces first), so the type
 // that decides the surface is that of PieceToId(IdToPiece(id)).
+int EnsurePieceStrings(spm_hip_model *m, bool dev);  // defined with the text-row entries
+
 int BuildDecodeTable(spm_hip_model *m) {
   static const char kSpace[] = "\xE2\x96\x81";  // U+2581
   const auto &ts = m->proto.trainer_spec;
@@ -1437,6 +1440,7 @@ static int LoadImpl(const void *model_proto, size_t len, spm_hip_model **out, bo
     else rc = Fail(SPM_UNIMPLEMENTED, "unknown model type");
   }
   if (rc == SPM_OK) rc = BuildDecodeTable(m);
+  if (rc == SPM_OK) rc = EnsurePieceStrings(m, !m->host_only);
   if (rc != SPM_OK) {
     spm_hip_model_free(m);
     return rc;
@@ -1503,7 +1507,8 @@ void spm_hip_model_free(spm_hip_model *m) {
   for (spm_amd::DevBuf *b : {&m->d_units, &m->d_uvs, &m->d_piece_tab, &m->d_values, &m->d_scores,
                              &m->bpe.pair_keys, &m->bpe.pair_vals, &m->bpe.pair_ent, &m->bpe.rank_piece, &m->bpe.entry_piece,
                              &m->bpe.entry_out, &m->bpe.piece_kind, &m->bpe.piece_out, &m->bpe.ud,
-                             &m->d_wc_tab, &m->d_wc_keys, &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_byte_ids, &m->d_types_kind, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes})
+                             &m->d_wc_tab, &m->d_wc_keys, &m->d_charsmap, &m->d_ud_units, &m->d_types, &m->d_byte_ids, &m->d_types_kind, &m->d_dec_meta, &m->d_dec_off, &m->d_dec_bytes, &m->d_pstr_off,
+                             &m->d_pstr_bytes})
     b->Release();
   for (auto &kv : m->by_stream) kv.second->Release();
   for (auto &w : m->host_pool) w->Release();
@@ -4026,6 +4031,127 @@ int spm_hip_fit_ids_host(const int32_t *ids, const uint64_t *off, uint64_t n, ui
   spm_amd::DenseFitHostLoop(ids, off, n, row_len, pad_id, flags, rows_capacity, out, seq, pos, row_lengths, place,
                             stats);
   return SPM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The piece strings of a model (text_rows.h); dev: also their device copy.  Runs at load, so
+// the text-row entries find both ready and stay pure stream calls.
+int EnsurePieceStrings(spm_hip_model *m, bool dev) {
+  if (dev ? m->pstr_dev_ready.load() : m->pstr_host_ready.load()) return SPM_OK;
+  std::lock_guard<std::mutex> g(m->init_mu);
+  if (!m->pstr_host_ready) {
+    uint64_t total = 0;
+    for (const auto &sp : m->proto.pieces) total += sp.piece.size();
+    if (total > 0xFFFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "piece strings exceed 4 GiB");
+    m->pstr_off.assign(m->proto.pieces.size() + 1, 0);
+    m->pstr_bytes.clear();
+    m->pstr_bytes.reserve(total);
+    for (size_t i = 0; i < m->proto.pieces.size(); ++i) {
+      const std::string &s = m->proto.pieces[i].piece;
+      m->pstr_bytes.insert(m->pstr_bytes.end(), s.begin(), s.end());
+      m->pstr_off[i + 1] = static_cast<uint32_t>(m->pstr_bytes.size());
+    }
+    m->pstr_host_ready = true;
+  }
+  if (dev && !m->pstr_dev_ready) {
+    SPM_HIP_TRY(Upload(&m->d_pstr_off, m->pstr_off));
+    SPM_HIP_TRY(Upload(&m->d_pstr_bytes, m->pstr_bytes));
+    m->pstr_dev_ready = true;
+  }
+  return SPM_OK;
+}
+
+int RowArgs(const void *off, uint64_t n, const void *out, const void *row_off) {
+  if (!off || !out || !row_off) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (n > 0x7FFFFFFFull) return Fail(SPM_INVALID_ARGUMENT, "too many rows in one batch");
+  return SPM_OK;
+}
+
+int ScratchArgs(const uint32_t *d_status, const void *d_scratch) {
+  if (!d_status || !d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 7))
+    return Fail(SPM_INVALID_ARGUMENT, "null status word, or scratch null or not 8-byte aligned");
+  return SPM_OK;
+}
+
+int RowStatus(int rc) {
+  if (rc == SPM_OUT_OF_RANGE) return Fail(rc, "an id or a piece span is out of range");
+  if (rc == SPM_RESOURCE_EXHAUSTED) return Fail(rc, "the output exceeds its capacity");
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spm_hip_split_lines(const uint8_t *d_text, uint64_t nbytes, uint8_t *d_out, uint64_t *d_off,
+                        uint64_t line_capacity, uint64_t *d_counts, uint32_t *d_status, void *d_scratch,
+                        void *stream) {
+  int rc = ScratchArgs(d_status, d_scratch);
+  if (rc != SPM_OK) return rc;
+  if (!d_off || (nbytes && (!d_text || !d_out))) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  spm_amd::TraceRange trace_range_("spm_hip_split_lines");
+  SPM_HIP_TRY(spm_amd::LaunchSplitLines(d_text, nbytes, d_out, d_off, line_capacity, d_counts, d_status, d_scratch,
+                                        static_cast<hipStream_t>(stream)));
+  return SPM_OK;
+}
+
+int spm_hip_split_lines_host(const uint8_t *text, uint64_t nbytes, uint8_t *out, uint64_t *off,
+                             uint64_t line_capacity, uint64_t *counts) {
+  if (!off || (nbytes && (!text || !out))) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  return RowStatus(spm_amd::SplitLinesHostLoop(text, nbytes, out, off, line_capacity, counts));
+}
+
+int spm_hip_format_id_rows(const int32_t *d_ids, const uint64_t *d_off, uint64_t n, uint8_t *d_out,
+                           uint64_t out_capacity, uint64_t *d_row_off, uint32_t *d_status, void *d_scratch,
+                           void *stream) {
+  int rc = ScratchArgs(d_status, d_scratch);
+  if (rc == SPM_OK) rc = RowArgs(d_off, n, d_out, d_row_off);
+  if (rc != SPM_OK) return rc;
+  spm_amd::TraceRange trace_range_("spm_hip_format_id_rows");
+  SPM_HIP_TRY(spm_amd::LaunchIdRows(d_ids, d_off, n, d_out, out_capacity, d_row_off, d_status, d_scratch,
+                                    static_cast<hipStream_t>(stream)));
+  return SPM_OK;
+}
+
+int spm_hip_format_id_rows_host(const int32_t *ids, const uint64_t *off, uint64_t n, uint8_t *out,
+                                uint64_t out_capacity, uint64_t *row_off) {
+  const int rc = RowArgs(off, n, out, row_off);
+  if (rc != SPM_OK) return rc;
+  return RowStatus(spm_amd::IdRowsHostLoop(ids, off, n, out, out_capacity, row_off));
+}
+
+int spm_hip_format_piece_rows(spm_hip_model *m, const spm_hip_piece *d_pieces, const uint64_t *d_piece_off,
+                              uint64_t n, const uint8_t *d_norm, const uint64_t *d_norm_off, uint8_t *d_out,
+                              uint64_t out_capacity, uint64_t *d_row_off, uint32_t *d_status, void *d_scratch,
+                              void *stream) {
+  if (!m || !d_norm_off) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  int rc = ScratchArgs(d_status, d_scratch);
+  if (rc == SPM_OK) rc = RowArgs(d_piece_off, n, d_out, d_row_off);
+  if (rc != SPM_OK) return rc;
+  if (m->host_only) return Fail(SPM_FAILED_PRECONDITION, "model was loaded host-only");
+  rc = EnsurePieceStrings(m, true);
+  if (rc != SPM_OK) return rc;
+  spm_amd::TraceRange trace_range_("spm_hip_format_piece_rows");
+  const spm_amd::PieceStrings tab{m->d_pstr_off.as<uint32_t>(), m->d_pstr_bytes.as<uint8_t>(),
+                                  static_cast<int32_t>(m->proto.pieces.size())};
+  SPM_HIP_TRY(spm_amd::LaunchPieceRows(d_pieces, d_piece_off, n, d_norm, d_norm_off, tab, d_out, out_capacity,
+                                       d_row_off, d_status, d_scratch, static_cast<hipStream_t>(stream)));
+  return SPM_OK;
+}
+
+int spm_hip_format_piece_rows_host(spm_hip_model *m, const spm_hip_piece *pieces, const uint64_t *piece_off,
+                                   uint64_t n, const uint8_t *norm, const uint64_t *norm_off, uint8_t *out,
+                                   uint64_t out_capacity, uint64_t *row_off) {
+  if (!m || !norm_off) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  int rc = RowArgs(piece_off, n, out, row_off);
+  if (rc == SPM_OK) rc = EnsurePieceStrings(m, false);
+  if (rc != SPM_OK) return rc;
+  return RowStatus(spm_amd::PieceRowsHostLoop(pieces, piece_off, n, norm, norm_off, m->pstr_off.data(),
+                                              m->pstr_bytes.data(), static_cast<int32_t>(m->proto.pieces.size()),
+                                              out, out_capacity, row_off));
 }
 
 }  // extern "C"

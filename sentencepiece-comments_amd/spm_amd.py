@@ -60,6 +60,8 @@ EXPORTED = [
     "spm_hip_model_byte_fallback", "spm_hip_finalize_ids_bytes", "spm_hip_finalize_ids_bytes_async",
     "spm_hip_pad_ids", "spm_hip_pack_ids", "spm_hip_pad_ids_host", "spm_hip_pack_ids_host",
     "spm_hip_fit_ids", "spm_hip_fit_ids_scratch_bytes", "spm_hip_fit_ids_host",
+    "spm_hip_split_lines", "spm_hip_split_lines_host", "spm_hip_format_id_rows", "spm_hip_format_id_rows_host",
+    "spm_hip_format_piece_rows", "spm_hip_format_piece_rows_host",
 ]
 # Flags of spm_hip_pad_ids (include/spm_hip.h).
 SPM_DENSE_PAD_LEFT, SPM_DENSE_TRUNCATE_LEFT, SPM_DENSE_KEEP_END = 1, 2, 4
@@ -281,6 +283,12 @@ def lib():
         L.spm_hip_fit_ids.argtypes = [P, P, U64, U32, I32, U32, U64, P, P, P, P, P, P, P, U64, P]
         L.spm_hip_fit_ids_scratch_bytes.argtypes = [U64, U32, U64, P]
         L.spm_hip_fit_ids_host.argtypes = [P, P, U64, U32, I32, U32, U64, P, P, P, P, P, P]
+        L.spm_hip_split_lines.argtypes = [P, U64, P, P, U64, P, P, P, P]
+        L.spm_hip_split_lines_host.argtypes = [P, U64, P, P, U64, P]
+        L.spm_hip_format_id_rows.argtypes = [P, P, U64, P, U64, P, P, P, P]
+        L.spm_hip_format_id_rows_host.argtypes = [P, P, U64, P, U64, P]
+        L.spm_hip_format_piece_rows.argtypes = [P, P, P, U64, P, P, P, U64, P, P, P, P]
+        L.spm_hip_format_piece_rows_host.argtypes = [P, P, P, U64, P, P, P, U64, P]
         _lib = L
     return _lib
 
@@ -366,6 +374,51 @@ def fit_ids_device(d_ids, d_off, n, row_len, pad_id, flags, rows_capacity, d_out
     _check(lib().spm_hip_fit_ids(_vp(d_ids), _vp(d_off), n, row_len, pad_id, flags, rows_capacity, _vp(d_out),
                                  _vp(d_seq), _vp(d_pos), _vp(d_row_lengths), _vp(d_place), _vp(d_stats),
                                  _vp(d_scratch), scratch_bytes, _vp(stream)))
+
+
+TEXT_ROWS_SCRATCH_BYTES = 16384  # SPM_HIP_TEXT_ROWS_SCRATCH_BYTES
+# Mirrors kTextBlocks, kSplitTile, kIdTile, kPieceTile of csrc/text_rows.h (blocks of every pass; bytes /
+# items of one tile): the GPU tests aim at tile edges with them.  Change both together.
+TEXT_BLOCKS, TEXT_SPLIT_TILE, TEXT_ID_TILE, TEXT_PIECE_TILE = 1024, 4096, 1024, 256
+SPM_RESOURCE_EXHAUSTED = 8
+
+
+def split_lines_device(d_text, nbytes, d_out, d_off, line_capacity, d_status, d_scratch, d_counts=None, stream=None):
+    """spm_hip_split_lines on device pointers (ints): a pure stream call, no model handle."""
+    _check(lib().spm_hip_split_lines(_vp(d_text), nbytes, _vp(d_out), _vp(d_off), line_capacity, _vp(d_counts),
+                                     _vp(d_status), _vp(d_scratch), _vp(stream)))
+
+
+def format_id_rows_device(d_ids, d_off, n, d_out, out_capacity, d_row_off, d_status, d_scratch, stream=None):
+    """spm_hip_format_id_rows on device pointers (ints): a pure stream call, no model handle."""
+    _check(lib().spm_hip_format_id_rows(_vp(d_ids), _vp(d_off), n, _vp(d_out), out_capacity, _vp(d_row_off),
+                                        _vp(d_status), _vp(d_scratch), _vp(stream)))
+
+
+def split_lines_host(text, line_capacity=None):
+    """spm_hip_split_lines_host (no GPU): (status, bytes uint8, off uint64[min(n, capacity) + 1], counts uint64[2])."""
+    buf = np.frombuffer(bytes(text), dtype=np.uint8)
+    cap = len(buf) if line_capacity is None else int(line_capacity)
+    out = np.zeros(max(len(buf), 1), dtype=np.uint8)
+    off = np.zeros(cap + 1, dtype=np.uint64)
+    counts = np.zeros(2, dtype=np.uint64)
+    rc = lib().spm_hip_split_lines_host(_p(buf) if len(buf) else None, len(buf), _p(out), _p(off), cap, _p(counts))
+    if rc not in (SPM_OK, SPM_RESOURCE_EXHAUSTED):
+        _check(rc)
+    return rc, out[:int(counts[1])], off[:min(int(counts[0]), cap) + 1], counts
+
+
+def format_id_rows_host(ids, off, capacity=None):
+    """spm_hip_format_id_rows_host on a numpy id CSR (no GPU): (status, text
+    bytes below the capacity, row_off uint64[n+1])."""
+    ids, off, n = _host_csr(ids, off)
+    cap = 11 * int(off[-1] - off[0]) + n if capacity is None else int(capacity)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    row_off = np.zeros(n + 1, dtype=np.uint64)
+    rc = lib().spm_hip_format_id_rows_host(_p(ids), _p(off), n, _p(out), cap, _p(row_off))
+    if rc not in (SPM_OK, SPM_RESOURCE_EXHAUSTED):
+        _check(rc)
+    return rc, out[:min(cap, int(row_off[-1]))].tobytes(), row_off
 
 
 def _host_csr(ids, off):
@@ -651,21 +704,9 @@ class DeviceModel:
         dev = torch.device("cuda", torch.cuda.current_device())
         buf, off = to_csr(lines)
         n = len(lines)
-        s = torch.cuda.current_stream(dev).cuda_stream
         d_in = torch.from_numpy(buf).to(dev)
         d_off = torch.from_numpy(off.view(np.int64)).to(dev)
-        cap = int(off[-1]) * 3 + 3 * n + 16
-        d_norm = torch.empty(cap, dtype=torch.uint8, device=dev)
-        d_noff = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        d_a = torch.empty(cap + n, dtype=torch.int32, device=dev)
-        pcap = cap + 2 * 32 * n
-        d_p = torch.empty(pcap * 5, dtype=torch.int32, device=dev)
-        d_po = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        tn, tp = ctypes.c_uint64(), ctypes.c_uint64()
-        _check(self._L.spm_hip_encode_spt(self.h, extra_options.encode(), d_in.data_ptr(), d_off.data_ptr(), n,
-                                          d_norm.data_ptr(), cap, d_noff.data_ptr(), d_a.data_ptr(),
-                                          d_p.data_ptr(), pcap, d_po.data_ptr(), ctypes.byref(tn),
-                                          ctypes.byref(tp), s))
+        d_norm, d_noff, d_p, d_po, tn, tp = self._spt_records_device(d_in, d_off, n, int(off[-1]), extra_options)
         torch.cuda.synchronize(dev)
         nb = d_norm[:tn.value].cpu().numpy().tobytes()
         no = d_noff.cpu().numpy()
@@ -682,6 +723,133 @@ class DeviceModel:
                 row.append((pid, piece, lines[i][b:e], b, e))
             out.append(row)
         return out
+
+    def _spt_records_device(self, d_in, d_off, n, raw_bytes, extra_options=""):
+        """spm_hip_encode_spt on a raw sentence CSR on the device: (d_norm,
+        d_norm_off, d_pieces int32[capacity * 5], d_piece_off, total_norm,
+        total_pieces), torch tensors and two ctypes counts."""
+        import torch
+        dev = d_in.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        cap = raw_bytes * 3 + 3 * n + 16
+        d_norm = torch.empty(cap, dtype=torch.uint8, device=dev)
+        d_noff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_a = torch.empty(cap + n, dtype=torch.int32, device=dev)
+        pcap = cap + 2 * 32 * n
+        d_p = torch.empty(pcap * 5, dtype=torch.int32, device=dev)
+        d_po = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        tn, tp = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._L.spm_hip_encode_spt(self.h, extra_options.encode(), d_in.data_ptr(), d_off.data_ptr(), n,
+                                          d_norm.data_ptr(), cap, d_noff.data_ptr(), d_a.data_ptr(),
+                                          d_p.data_ptr(), pcap, d_po.data_ptr(), ctypes.byref(tn),
+                                          ctypes.byref(tp), s))
+        return d_norm, d_noff, d_p, d_po, tn, tp
+
+    split_lines_device = staticmethod(split_lines_device)
+    format_id_rows_device = staticmethod(format_id_rows_device)
+
+    def format_piece_rows_device(self, d_pieces, d_piece_off, n, d_norm, d_norm_off, d_out, out_capacity, d_row_off,
+                                 d_status, d_scratch, stream=None):
+        """spm_hip_format_piece_rows on device pointers (ints): a pure stream call."""
+        _check(self._L.spm_hip_format_piece_rows(self.h, _vp(d_pieces), _vp(d_piece_off), n, _vp(d_norm),
+                                                 _vp(d_norm_off), _vp(d_out), out_capacity, _vp(d_row_off),
+                                                 _vp(d_status), _vp(d_scratch), _vp(stream)))
+
+    def format_piece_rows_host(self, pieces, piece_off, norm, norm_off, capacity):
+        """spm_hip_format_piece_rows_host (no GPU; works host-only).  pieces:
+        int32[k, 5] records (id, begin, end, norm_begin, norm_end).  Returns
+        (status, text bytes below the capacity, row_off uint64[n+1])."""
+        pieces = np.ascontiguousarray(pieces, dtype=np.int32).reshape(-1, 5)
+        piece_off = np.ascontiguousarray(piece_off, dtype=np.uint64)
+        norm_off = np.ascontiguousarray(norm_off, dtype=np.uint64)
+        norm = np.frombuffer(bytes(norm) + b"\0", dtype=np.uint8)
+        n = len(piece_off) - 1
+        out = np.zeros(max(int(capacity), 1), dtype=np.uint8)
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        if pieces.size == 0:
+            pieces = np.zeros((1, 5), dtype=np.int32)
+        rc = self._L.spm_hip_format_piece_rows_host(self.h, _p(pieces), _p(piece_off), n, _p(norm), _p(norm_off),
+                                                    _p(out), int(capacity), _p(row_off))
+        if rc not in (SPM_OK, SPM_RESOURCE_EXHAUSTED):
+            _check(rc)
+        return rc, out[:min(int(capacity), int(row_off[-1]))].tobytes(), row_off
+
+    def split_text_device(self, text):
+        """A text buffer (bytes) -> (d_bytes uint8, d_off int64[n+1], n, line
+        bytes): spm_hip_split_lines on the current stream.  The line capacity
+        is a guess (one line per 16 bytes); a buffer with more lines runs a
+        second time with the count the first run reported.  One blocking
+        read-back of the status and counts per run."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        s = torch.cuda.current_stream(dev).cuda_stream
+        nbytes = len(text)
+        d_text = torch.from_numpy(np.frombuffer(bytes(text) + b"\0", dtype=np.uint8).copy()).to(dev)
+        d_out = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        scratch = torch.empty(TEXT_ROWS_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+        cap = nbytes // 16 + 16
+        while True:
+            d_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            ctl = torch.zeros(3, dtype=torch.int64, device=dev)  # status word, counts
+            split_lines_device(d_text.data_ptr(), nbytes, d_out.data_ptr(), d_off.data_ptr(), cap, ctl.data_ptr(),
+                               scratch.data_ptr(), d_counts=ctl.data_ptr() + 8, stream=s)
+            status, n, line_bytes = (int(x) for x in ctl.tolist())
+            if status == SPM_OK:
+                return d_out, d_off[:n + 1], n, line_bytes
+            if status != SPM_RESOURCE_EXHAUSTED:
+                raise SpmError(status, "spm_hip_split_lines")
+            cap = n
+
+    def encode_text_rows(self, text, fmt, extra_options=""):
+        """A text buffer (bytes, lines separated by '\\n') -> the bytes
+        spm_encode prints for it with --output_format=id or piece (fmt "id" /
+        "piece"): split, normalize, encode, epilogue and format all on the
+        device.  One upload of the text and one copy back of the rows; besides
+        those, word-sized blocking read-backs for sizes (the split's counts,
+        the encode's totals, the rows' size and status), and the split or the
+        piece format runs twice when its first capacity guess was short."""
+        import torch
+        if fmt not in ("id", "piece"):
+            raise SpmError(SPM_INVALID_ARGUMENT, "fmt must be 'id' or 'piece'")
+        if self.info().model_type not in (SPM_UNIGRAM, SPM_BPE):
+            # As SentencePieceProcessor::TextRowsSupported: the host epilogue of WORD / CHAR models
+            # fails a line that spells a CONTROL piece, the device epilogue has no such check.
+            raise SpmError(12, "text rows: WORD / CHAR models take their rows from the host path")
+        d_lines, d_off, n, line_bytes = self.split_text_device(text)
+        if n == 0:
+            return b""
+        dev = d_lines.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        scratch = torch.empty(TEXT_ROWS_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        d_roff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if fmt == "id":
+            d_ids, d_ooff, k = self._device_csr_to_id_csr(d_lines, d_off, n, line_bytes, extra_options)
+            cap = 11 * k + n
+            d_text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            format_id_rows_device(d_ids.data_ptr(), d_ooff.data_ptr(), n, d_text.data_ptr(), cap, d_roff.data_ptr(),
+                                  status.data_ptr(), scratch.data_ptr(), stream=s)
+        else:
+            d_norm, d_noff, d_p, d_po, tn, tp = self._spt_records_device(d_lines, d_off, n, line_bytes,
+                                                                         extra_options)
+            # Enough unless many records take their piece from the table (bos /
+            # eos, BYTE pieces); a text that does not fit reports its size in
+            # row_off[n] and the call runs again.
+            cap = tn.value + 8 * tp.value + n
+            while True:
+                d_text = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+                self.format_piece_rows_device(d_p.data_ptr(), d_po.data_ptr(), n, d_norm.data_ptr(),
+                                              d_noff.data_ptr(), d_text.data_ptr(), cap, d_roff.data_ptr(),
+                                              status.data_ptr(), scratch.data_ptr(), stream=s)
+                if int(status[0].item()) != SPM_RESOURCE_EXHAUSTED:
+                    break
+                cap = int(d_roff[n].item())
+                status.zero_()
+        total = int(d_roff[n].item())
+        st = int(status[0].item())
+        if st != SPM_OK:
+            raise SpmError(st, "text rows")
+        return d_text[:total].cpu().numpy().tobytes()
 
     def encode_csr_host(self, buf, off, with_lens=False):
         """Host CSR in → (ids int32, [piece_len uint32], tok_off uint64[n+1])."""
@@ -1099,11 +1267,16 @@ class DeviceModel:
         import torch
         dev = torch.device("cuda", torch.cuda.current_device())
         buf, off = to_csr(lines)
-        n = len(lines)
-        s = torch.cuda.current_stream(dev).cuda_stream
         d_in = torch.from_numpy(buf).to(dev)
         d_off = torch.from_numpy(off.view(np.int64)).to(dev)
-        cap = int(off[-1]) * 3 + 3 * n + 16
+        return self._device_csr_to_id_csr(d_in, d_off, len(lines), int(off[-1]), extra_options, sample)
+
+    def _device_csr_to_id_csr(self, d_in, d_off, n, raw_bytes, extra_options="", sample=None):
+        """_lines_to_id_csr from a raw sentence CSR that is on the device already."""
+        import torch
+        dev = d_in.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        cap = raw_bytes * 3 + 3 * n + 16
         d_norm = torch.empty(cap, dtype=torch.uint8, device=dev)
         d_noff = torch.empty(n + 1, dtype=torch.int64, device=dev)
         tot = ctypes.c_uint64()
