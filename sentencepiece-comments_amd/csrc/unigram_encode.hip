@@ -405,8 +405,7 @@ void unigram_fast_kernel(FastArgs a) {
     // Window: aligned dwords of the lane's bytes, spliced by alignbyte.
     const uint32_t sh = lrel & 3u;
     const uint32_t lane_al = lrel & ~3u;
-    auto word_at = [&](uint32_t m) -> uint32_t {
-      const uint32_t o = lane_al + 4u * m;
+    auto word_at_off = [&](uint32_t o) -> uint32_t {  // o: the dword's offset in the tile's bytes
       if (o + 4 <= blk_rem) return __builtin_amdgcn_raw_buffer_load_b32(bytes_rsrc, o, 0, 0);
       // The batch's last, partial dword: byte loads (a dword load that
       // straddles num_records would read as 0).
@@ -416,10 +415,15 @@ void unigram_fast_kernel(FastArgs a) {
         if (o + t < blk_rem) x |= static_cast<uint32_t>(a.bytes[blk_al + o + t]) << (8 * t);
       return x;
     };
+    auto word_at = [&](uint32_t m) -> uint32_t { return word_at_off(lane_al + 4u * m); };
     // Bytes q .. q+3 with zeros beyond nb; a 0xFF byte (the padded trie image
     // matches 0xFF on empty units) flags the sentence.
-    auto finish = [&](uint32_t x, uint32_t q) -> uint32_t {
+    auto mask_to_nb = [&](uint32_t x, uint32_t q) -> uint32_t {
       if (q + 4 > nb) x &= q >= nb ? 0u : (1u << (8 * (nb - q))) - 1u;
+      return x;
+    };
+    auto finish = [&](uint32_t x, uint32_t q) -> uint32_t {
+      x = mask_to_nb(x, q);
       const uint32_t y = ~x;
       if (((y - 0x01010101u) & ~y & 0x80808080u) != 0) bad = true;
       return x;
@@ -433,6 +437,10 @@ void unigram_fast_kernel(FastArgs a) {
       rw[k] = q < nb ? finish(__builtin_amdgcn_alignbyte(wn, wprev, sh), q) : 0u;
       wprev = wn;
     }
+    // Encode: the word behind the window, fetched together with the window's
+    // last one (see the loop's end).  The E-step mode fetches one word per group.
+    constexpr bool kPairWin = !kE;
+    [[maybe_unused]] uint32_t rw_next = 0u;
     auto byte_of = [&](auto tc) -> uint32_t {
       constexpr int t = decltype(tc)::value;
       return (rw[t >> 2] >> (8 * (t & 3))) & 0xFFu;
@@ -816,9 +824,58 @@ void unigram_fast_kernel(FastArgs a) {
 #pragma unroll
       for (int k = 0; k + 1 < kWin; ++k) rw[k] = rw[k + 1];
       const uint32_t qn = p0 + kU + 4 * (kWin - 1);
-      const uint32_t wn = qn < nb ? word_at(qn / 4 + 1) : 0u;
-      rw[kWin - 1] = qn < nb ? finish(__builtin_amdgcn_alignbyte(wn, wprev, sh), qn) : 0u;
-      wprev = wn;
+      if constexpr (kPairWin) {
+        // The window advances 8 bytes every other group.  p0 is the same for
+        // the whole wave, so this is a scalar branch: an even group (p0 a
+        // multiple of 8) fetches the next two dwords at once and prepares
+        // both window words, rw_next the one that the odd group after it
+        // shifts in without a fetch.  The address, the range test and the
+        // update of `bad` are shared by the two words.
+        if ((p0 & 4u) == 0) {
+          uint32_t x0 = 0u, x1 = 0u;
+          if (qn < nb) {
+            // The dword behind byte qn, lane_al + qn + 4, and the splice's
+            // byte shift both come from lrel here (v_alignbyte reads the low
+            // two bits of its shift operand, and qn + 4 is a multiple of 4),
+            // so neither lane_al nor sh holds a register through the walk:
+            // the second window word's register is paid for by theirs.  The
+            // empty asm keeps the sum from being split into a loop-invariant
+            // part again.
+            uint32_t l = lrel + (qn + 4u);
+            __asm__ volatile("" : "+v"(l));
+            const uint32_t o = l & ~3u;
+            const bool two = qn + 4 < nb;  // the second word holds a byte of the sentence
+            uint32_t w0, w1;
+            // Both dwords inside the resource: one 8-byte load (it needs
+            // 4-byte alignment only).  One that straddles num_records would
+            // read as 0, so near the end of the bytes each word goes
+            // word_at's way, byte by byte for the batch's last partial dword.
+            if (o + 8 <= blk_rem) {
+              const auto w = __builtin_amdgcn_raw_buffer_load_b64(bytes_rsrc, o, 0, 0);
+              w0 = w[0];
+              w1 = w[1];
+            } else {
+              w0 = word_at_off(o);
+              w1 = two ? word_at_off(o + 4u) : 0u;
+            }
+            // Bytes at or past nb read as 0, then the 0xFF test of both
+            // words at once.
+            x0 = mask_to_nb(__builtin_amdgcn_alignbyte(w0, wprev, l), qn);
+            x1 = two ? mask_to_nb(__builtin_amdgcn_alignbyte(w1, w0, l), qn + 4) : 0u;
+            const uint32_t y0 = ~x0, y1 = ~x1;
+            if ((((y0 - 0x01010101u) & ~y0) | ((y1 - 0x01010101u) & ~y1)) & 0x80808080u) bad = true;
+            wprev = w1;
+          }
+          rw[kWin - 1] = x0;
+          rw_next = x1;
+        } else {
+          rw[kWin - 1] = rw_next;
+        }
+      } else {
+        const uint32_t wn = qn < nb ? word_at(qn / 4 + 1) : 0u;
+        rw[kWin - 1] = qn < nb ? finish(__builtin_amdgcn_alignbyte(wn, wprev, sh), qn) : 0u;
+        wprev = wn;
+      }
     }
   } else if constexpr (kWide) {
     // ---- Wide-char pass (models whose pieces are whole chars, < 16 chars,

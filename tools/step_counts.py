@@ -43,7 +43,18 @@ def fmt(c):
     return "v_ %3d  s_ %3d (branches %2d)  ds_ %d  stores %d" % (c["v_"], c["s_"], c["branch"], c["lds"], c["store"])
 
 
-def prologue(ops, sub):
+REG = re.compile(r"^(v\d+|v\[\d+:\d+\]|s\d+|s\[\d+:\d+\])$")
+
+
+def is_reg_move(op, arg):
+    """A vector move whose source is a register: it computes nothing."""
+    if not op.startswith(("v_mov_b32", "v_mov_b64", "v_pk_mov_b32")):
+        return False
+    parts = [x.strip() for x in arg.split(",")]
+    return len(parts) >= 2 and bool(REG.match(parts[1]))
+
+
+def prologue(ops, sub, args):
     """--prologue: the byte kernel's forward pass outside its walk steps.
 
     pair prologue k: the stretch that ends at pair k's two root-table reads
@@ -54,8 +65,22 @@ def prologue(ops, sub):
     back-pointer store: every byte store of the forward loop with its guard,
       from the s_and_saveexec that opens it to the s_or_b64 exec that closes it.
     group epilogue: the stretch between two unconditional branches that holds
-      the loop's window load (the first buffer_load_dword after the last root
-      read): back-pointer word store, ring shift, window advance."""
+      the window's splice (the first v_alignbyte_b32 after the last root
+      read): back-pointer word store, ring shift, window advance.  Blocks laid
+      out behind the closing branch (the byte-wise tail of the batch's last
+      partial dword, a guarded load) are not in it.
+    The three rows under it split the group's end, from the branch before the
+    shift to the closing branch:
+      ring shift: the last cluster of three or more register-to-register
+        vector moves before the splice (at most 8 instructions apart): score ring,
+        back-pointer words and whatever of the window's rotation sits there,
+        32-bit and 64-bit moves counted apart.
+      window advance: the vector instructions other than such moves from the
+        last back-pointer store (or the stretch's start) to the closing
+        branch, and the loads among them.  It holds the one compare of the
+        near-tie mask's refresh.
+      the rest: every other vector instruction from the branch before the
+        shift to the closing branch (back-pointer stores, defaults)."""
     roots = [n for n in range(len(ops) - 1) if ops[n] == "ds_read_b64" and ops[n + 1] == "ds_read_b64"]
     if not roots:
         sys.exit("no root-table reads (not a byte-kernel instantiation)")
@@ -68,7 +93,7 @@ def prologue(ops, sub):
 
     for k, r in enumerate(roots):
         print("pair prologue %d        %s" % (k, fmt(count(ops[back_to_branch(r):r]))))
-    win = next(n for n in range(roots[-1], len(ops)) if ops[n] == "buffer_load_dword")
+    win = next(n for n in range(roots[-1], len(ops)) if ops[n] == "v_alignbyte_b32")
     stores = [n for n in range(roots[0] - 80, win) if ops[n] in ("ds_write_b8", "ds_write_b8_d16_hi", "buffer_store_byte")]
     # A site: the stores at most 12 instructions apart (the scratch and the LDS side of one guarded store).
     groups = []
@@ -96,6 +121,27 @@ def prologue(ops, sub):
     # (The word store's block may be laid out behind the stretch's closing branch.)
     print("group epilogue         %s  (v_mov %d; ds_write_b32 in it or in the 60 instructions behind it: %d)" % (
         fmt(c), sum(o.startswith("v_mov") for o in seg), sum(o == "ds_write_b32" for o in ops[e0:e1 + 61])))
+    moves = [n for n in range(roots[-1], win) if is_reg_move(ops[n], args[n])]
+    clusters = []
+    for n in moves:
+        if clusters and n - clusters[-1][-1] <= 8:
+            clusters[-1].append(n)
+        else:
+            clusters.append([n])
+    # (A lone copy that widens an offset for a 64-bit compare is no shift.)
+    shift = next((c for c in reversed(clusters) if len(c) >= 3), [])
+    g0 = back_to_branch(shift[0]) if shift else e0
+    last_store = max([n for n in range(g0, win) if ops[n] in ("ds_write_b32", "buffer_store_byte")], default=e0 - 1)
+    w0 = max(e0, last_store + 1)
+    adv = [n for n in range(w0, e1 + 1) if ops[n].startswith("v_") and n not in shift and not is_reg_move(ops[n], args[n])]
+    rest = [n for n in range(g0, e1 + 1) if ops[n].startswith("v_") and n not in shift and n not in adv]
+    print("  ring shift           v_ %3d  (v_mov_b32 %d, v_mov_b64 %d, v_pk_mov_b32 %d)" % (
+        len(shift), sum(ops[n].startswith("v_mov_b32") for n in shift), sum(ops[n].startswith("v_mov_b64") for n in shift),
+        sum(ops[n].startswith("v_pk_mov") for n in shift)))
+    print("  window advance       v_ %3d  (loads: %s)" % (
+        len(adv), ", ".join(sorted({ops[n] for n in range(w0, e1 + 1) if "_load_" in ops[n]})) or "laid out behind"))
+    print("  the rest             v_ %3d  (from the branch before the shift, %d instructions before the splice)" % (
+        len(rest), win - g0))
 
 
 def main():
@@ -103,13 +149,14 @@ def main():
     path = argv[0]
     sub = argv[1] if len(argv) > 1 else DEFAULT
     body = kernel_body(open(path).read().split("\n"), sub)
-    ops = []
+    ops, args = [], []
     for ln in body:
-        m = re.match(r"\s+([a-z_0-9]+)", ln)
+        m = re.match(r"\s+([a-z_0-9]+)(.*)", ln)
         if m and not ln.lstrip().startswith((".", ";")):
             ops.append(m.group(1))
+            args.append(m.group(2).split(";")[0].strip())
     if "--prologue" in sys.argv[1:]:
-        prologue(ops, sub)
+        prologue(ops, sub, args)
         return
     loads = [n for n, o in enumerate(ops) if o == "buffer_load_dwordx2"]
     # A pair: two gathers at most 8 instructions apart.
