@@ -1160,6 +1160,52 @@ int spm_hip_fit_ids_host(const int32_t *ids, const uint64_t *offsets, uint64_t n
                          int32_t pad_id, uint32_t flags, uint64_t rows_capacity, int32_t *out, int32_t *seq,
                          int32_t *pos, int32_t *row_lengths, uint64_t *place, uint64_t *stats);
 
+/* Window: a sentence longer than a row as several rows of row_len = L that
+ * overlap by stride = S tokens (the layout of sliding-window perplexity and
+ * of embedding or QA over long passages; other tokenizer libraries call it
+ * stride with overflowing tokens).  d_ids / d_offsets[n+1] as for pad.  h and
+ * t are 1 when SPM_WINDOW_KEEP_FIRST and SPM_WINDOW_KEEP_LAST are set, else
+ * 0; C = L - h - t is the payload of a row and step = C - S.  C >= 1 and
+ * 0 <= S < C are required.  Sentence i of len tokens:
+ *   len <= h + t: one row that holds the len tokens as they are (len = 0: a
+ *     row of pads).
+ *   else the body is tokens [h, len - t), m = len - h - t of them: one row if
+ *     m <= C, else r_i = 1 + ceil((m - C) / step) rows.  Row w of the sentence
+ *     holds token 0 if h, then body tokens [w * step, min(w * step + C, m)),
+ *     then token len - 1 if t, then pad_id.  The last row is short, not
+ *     right-aligned.
+ * The rows of sentence i follow those of sentence i - 1; every sentence has
+ * at least one row.  Outputs: d_out[rows_capacity*L]; nullable d_pos (int32
+ * per slot: the token's index in its sentence, 0 on padding), d_fresh (uint8
+ * per slot: 1 iff no earlier row carries that token, so over the rows of a
+ * sentence exactly len slots are fresh; 0 on padding), d_lengths[rows] (int32:
+ * the used slots of a row), d_row_sentence[rows] (int32: i), d_first_row[n+1]
+ * (uint64: the CSR of rows per sentence) and d_stats[2] (uint64: rows needed
+ * R, sentences with more than one row).  Rows at or past rows_capacity are
+ * not written, rows in [R, rows_capacity) are not touched; d_first_row and
+ * d_stats are always complete.  Sizing: R <= n + floor(T / step) with T the
+ * token total.  The device call works in d_scratch (device memory, 16-byte
+ * aligned, contents undefined before and after), scratch_bytes of it, at
+ * least what spm_hip_window_ids_scratch_bytes returns for n (host only; 0 for
+ * n == 0, when d_scratch may be null); too little is SPM_INVALID_ARGUMENT.  It
+ * is a pure stream call as the other dense entries are.  SPM_INVALID_ARGUMENT:
+ * an unknown flag bit, a null d_out or d_offsets, row_len == 0 or > INT32_MAX,
+ * C < 1, S >= C.  SPM_OUT_OF_RANGE: n > INT32_MAX.  n == 0 is fine:
+ * d_first_row = {0}, d_stats = {0, 0}.  The _host form takes host pointers and
+ * no scratch and runs the same rule in a plain loop on the calling thread. */
+#define SPM_WINDOW_KEEP_FIRST 0x1u
+#define SPM_WINDOW_KEEP_LAST 0x2u
+int spm_hip_window_ids(const int32_t *d_ids, const uint64_t *d_offsets, uint64_t n, uint32_t row_len,
+                       uint32_t stride, int32_t pad_id, uint32_t flags, uint64_t rows_capacity, int32_t *d_out,
+                       int32_t *d_pos, uint8_t *d_fresh, int32_t *d_lengths, int32_t *d_row_sentence,
+                       uint64_t *d_first_row, uint64_t *d_stats, void *d_scratch, uint64_t scratch_bytes,
+                       void *stream);
+int spm_hip_window_ids_scratch_bytes(uint64_t n, uint64_t *bytes);
+int spm_hip_window_ids_host(const int32_t *ids, const uint64_t *offsets, uint64_t n, uint32_t row_len,
+                            uint32_t stride, int32_t pad_id, uint32_t flags, uint64_t rows_capacity, int32_t *out,
+                            int32_t *pos, uint8_t *fresh, int32_t *lengths, int32_t *row_sentence,
+                            uint64_t *first_row, uint64_t *stats);
+
 /* Text rows: the text around a corpus run, on the device.  spm_encode reads
  * lines and prints one row of ids or pieces per line; these three calls do
  * both ends without a host loop over lines, ids or pieces.  No reference

@@ -11,6 +11,8 @@
 //   fit : whole sentences share a row and none is split (in-order next-fit):
 //         a sentence that does not fit into what is left of the row opens the
 //         next row; one longer than a row is cut to the row.
+// The fourth layout, window (a long sentence as rows that overlap by a
+// stride), has its rule in dense_window.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -382,7 +382,8 @@ namespace {
 enum {
   kIn, kInOff, kNorm, kNormOff, kIds, kLen, kTok, kOut, kOutOff, kSmallBlockSlot, kCounts,
   kDenseIds, kDenseAux0, kDenseAux1, kDenseStats, kDenseScratch, kDenseRowLengths, kDensePlace,
-  kTrText, kTrLines, kTrOff, kTrCtl, kTrScratch, kTrRows, kTrRowOff, kTrAlign, kTrPieces, kTrPieceOff
+  kTrText, kTrLines, kTrOff, kTrCtl, kTrScratch, kTrRows, kTrRowOff, kTrAlign, kTrPieces, kTrPieceOff,
+  kDenseFresh
 };
 }  // namespace
 
@@ -838,6 +839,8 @@ Status SentencePieceProcessor::RunDense(const std::vector<std::string> &inputs, 
                   : o.pack ? 0u
                            : SPM_DENSE_PAD_LEFT | SPM_DENSE_TRUNCATE_LEFT | SPM_DENSE_KEEP_END))
     return Err(SPM_INVALID_ARGUMENT, "unknown dense flag bit");
+  if (o.window && (o.pack || o.whole || o.flags))
+    return Err(SPM_INVALID_ARGUMENT, "window takes neither pack, whole nor dense flags");
   *out = DenseBatch();
   out->row_len = o.row_len;
   if (host_ids) host_ids->clear();
@@ -872,6 +875,48 @@ Status SentencePieceProcessor::RunDense(const std::vector<std::string> &inputs, 
     if (!st.ok()) return st;
     st = DeviceFinalize(b, n, &d_csr, &d_csr_off, &fin);
     if (!st.ok()) return st;
+  }
+  if (o.window) {
+    // The bound of spm_hip_window_ids; the rows needed are read back.
+    const uint32_t wflags = (o.keep_first ? SPM_WINDOW_KEEP_FIRST : 0u) | (o.keep_last ? SPM_WINDOW_KEEP_LAST : 0u);
+    const uint64_t kept = (o.keep_first ? 1 : 0) + (o.keep_last ? 1 : 0);
+    if (L <= kept || o.stride >= L - kept)
+      return Err(SPM_INVALID_ARGUMENT, "row_len leaves no payload beside the kept tokens, or stride >= the payload");
+    const uint64_t cap = n + fin / (L - kept - o.stride);
+    if (cap > std::numeric_limits<uint64_t>::max() / (4 * L)) return Err(SPM_OUT_OF_RANGE, "rows * row_len is too large");
+    uint64_t scratch_bytes = 0;
+    Status ws = FromC(spm_hip_window_ids_scratch_bytes(n, &scratch_bytes));
+    if (!ws.ok()) return ws;
+    int32_t *d_ids = static_cast<int32_t *>(dev_.Get(kDenseIds, cap * L * 4));
+    int32_t *d_pos = static_cast<int32_t *>(dev_.Get(kDenseAux1, cap * L * 4));
+    uint8_t *d_fresh = static_cast<uint8_t *>(dev_.Get(kDenseFresh, cap * L));
+    int32_t *d_len = static_cast<int32_t *>(dev_.Get(kDenseAux0, cap * 4));
+    int32_t *d_rs = static_cast<int32_t *>(dev_.Get(kDenseRowLengths, cap * 4));
+    uint64_t *d_fr = static_cast<uint64_t *>(dev_.Get(kDensePlace, (n + 1) * 8));
+    uint64_t *d_stats = static_cast<uint64_t *>(dev_.Get(kDenseStats, 32));
+    void *d_scratch = dev_.Get(kDenseScratch, scratch_bytes);
+    if (!d_ids || !d_pos || !d_fresh || !d_len || !d_rs || !d_fr || !d_stats || !d_scratch)
+      return Err(SPM_RESOURCE_EXHAUSTED, "device allocation failed");
+    ws = FromC(spm_hip_window_ids(d_csr, d_csr_off, n, o.row_len, o.stride, o.pad_id, wflags, cap, d_ids, d_pos,
+                                  d_fresh, d_len, d_rs, d_fr, d_stats, d_scratch, scratch_bytes, nullptr));
+    if (!ws.ok()) return ws;
+    uint64_t stats[2] = {0, 0};
+    if ((he = hipMemcpy(stats, d_stats, 16, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(he);
+    out->ids = d_ids;
+    out->pos = d_pos;
+    out->fresh = d_fresh;
+    out->lengths = d_len;
+    out->row_sentence = d_rs;
+    out->first_row = d_fr;
+    out->stats = d_stats;
+    out->rows = stats[0];
+    out->tokens = fin;
+    if (host_ids) {
+      host_ids->resize(stats[0] * L);
+      if (stats[0] && (he = hipMemcpy(host_ids->data(), d_ids, stats[0] * L * 4, hipMemcpyDeviceToHost)) != hipSuccess)
+        return fail_hip(he);
+    }
+    return Status::Ok();
   }
   // Pack: the row count comes from the id count the epilogue returned.
   // Whole: the bound of spm_hip_fit_ids; the rows needed are read back below.

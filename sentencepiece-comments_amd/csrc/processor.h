@@ -148,14 +148,21 @@ class SentencePieceProcessor {
   // SPM_DENSE_KEEP_END).  pack = true: the lines' ids run on as one stream of
   // row_len slots per row (flags must be 0).  pack and whole: whole lines share
   // a row and none is split (spm_hip_fit_ids; flags: SPM_DENSE_TRUNCATE_LEFT,
-  // SPM_DENSE_KEEP_END for a line longer than a row).  The extra options are
-  // part of the ids, so they apply before padding.
+  // SPM_DENSE_KEEP_END for a line longer than a row).  window: a line longer
+  // than a row becomes several rows that overlap by `stride` tokens
+  // (spm_hip_window_ids; pack, whole and flags must be unset; keep_first /
+  // keep_last repeat the line's first / last token, a bos / eos of the extra
+  // options, in every row).  The extra options are part of the ids, so they
+  // apply before padding.
   struct DenseOptions {
     uint32_t row_len = 0;
     int32_t pad_id = 0;
     uint32_t flags = 0;
     bool pack = false;
     bool whole = false;  // meaningful with pack
+    bool window = false;
+    uint32_t stride = 0;  // window: tokens two consecutive rows of a line share
+    bool keep_first = false, keep_last = false;
   };
   // Device pointers, owned by the processor and valid until the next call on
   // the instance; the work that fills them is enqueued on the null stream.
@@ -175,6 +182,11 @@ class SentencePieceProcessor {
     uint64_t cut = 0, dropped = 0;
     const int32_t *row_lengths = nullptr;  // whole: [rows], the used slots of a row
     const uint64_t *place = nullptr;       // whole: [lines], row * row_len + first column, UINT64_MAX if empty
+    // window: ids, pos, lengths ([rows], the used slots of a row), stats = {rows, lines with more than one row},
+    // rows = the rows needed (the call waits for the device to read them), and:
+    const uint8_t *fresh = nullptr;         // [rows, row_len], 1 where no earlier row carries the token
+    const int32_t *row_sentence = nullptr;  // [rows], the row's line
+    const uint64_t *first_row = nullptr;    // [lines + 1], the CSR of rows per line
   };
   // Nothing but the id count comes back to the host unless host_ids is given
   // (then it receives the rows * row_len ids).  A WORD or CHAR model takes its
@@ -330,8 +342,8 @@ class SentencePieceProcessor {
                       uint64_t count, std::vector<std::pair<std::string, int>> *out) const;
   // Grow-only device staging for EncodeBatch (raw lines → normalized → ids).
   struct Staging {
-    void *ptr[28] = {};
-    size_t cap[28] = {};
+    void *ptr[29] = {};
+    size_t cap[29] = {};
     void *Get(int k, size_t bytes);
     ~Staging();
   };

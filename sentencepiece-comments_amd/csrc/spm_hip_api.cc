@@ -20,6 +20,7 @@
 #include "../../include/spm_hip.h"
 #include "bpe_tables.h"
 #include "dense.h"
+#include "dense_window.h"
 #include "text_rows.h"
 #include "device_model.h"
 #include "epilogue.h"
@@ -4030,6 +4031,62 @@ int spm_hip_fit_ids_host(const int32_t *ids, const uint64_t *off, uint64_t n, ui
   if (rc != SPM_OK) return rc;
   spm_amd::DenseFitHostLoop(ids, off, n, row_len, pad_id, flags, rows_capacity, out, seq, pos, row_lengths, place,
                             stats);
+  return SPM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int WindowArgs(const uint64_t *off, uint64_t n, uint32_t row_len, uint32_t stride, uint32_t flags, const int32_t *out,
+               uint64_t *rows_capacity, spm_amd::WindowGeom *g) {
+  if (!off || !out) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (row_len == 0 || row_len > 0x7FFFFFFFu) return Fail(SPM_INVALID_ARGUMENT, "row_len must be in [1, INT32_MAX]");
+  if (flags & ~spm_amd::kWindowFlagMask) return Fail(SPM_INVALID_ARGUMENT, "unknown window flag bit");
+  if (!spm_amd::WindowGeomFor(row_len, stride, flags, g))
+    return Fail(SPM_INVALID_ARGUMENT, "row_len leaves no payload beside the kept tokens, or stride >= the payload");
+  if (n > 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  *rows_capacity = std::min(*rows_capacity, std::numeric_limits<uint64_t>::max() / row_len);
+  return SPM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spm_hip_window_ids_scratch_bytes(uint64_t n, uint64_t *bytes) {
+  if (!bytes) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  if (n > 0x7FFFFFFFull) return Fail(SPM_OUT_OF_RANGE, "too many sentences in one batch");
+  *bytes = spm_amd::WindowPlanFor(n).bytes;
+  return SPM_OK;
+}
+
+int spm_hip_window_ids(const int32_t *d_ids, const uint64_t *d_off, uint64_t n, uint32_t row_len, uint32_t stride,
+                       int32_t pad_id, uint32_t flags, uint64_t rows_capacity, int32_t *d_out, int32_t *d_pos,
+                       uint8_t *d_fresh, int32_t *d_lengths, int32_t *d_row_sentence, uint64_t *d_first_row,
+                       uint64_t *d_stats, void *d_scratch, uint64_t scratch_bytes, void *stream) {
+  spm_amd::WindowGeom g;
+  const int rc = WindowArgs(d_off, n, row_len, stride, flags, d_out, &rows_capacity, &g);
+  if (rc != SPM_OK) return rc;
+  if (n && (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15) || scratch_bytes < spm_amd::WindowPlanFor(n).bytes))
+    return Fail(SPM_INVALID_ARGUMENT,
+                "scratch is null, not 16-byte aligned or smaller than spm_hip_window_ids_scratch_bytes");
+  spm_amd::TraceRange trace_range_("spm_hip_window_ids");
+  SPM_HIP_TRY(spm_amd::LaunchDenseWindow(d_ids, d_off, n, g, pad_id, rows_capacity, d_out, d_pos, d_fresh, d_lengths,
+                                         d_row_sentence, d_first_row, d_stats, d_scratch,
+                                         static_cast<hipStream_t>(stream)));
+  return SPM_OK;
+}
+
+int spm_hip_window_ids_host(const int32_t *ids, const uint64_t *off, uint64_t n, uint32_t row_len, uint32_t stride,
+                            int32_t pad_id, uint32_t flags, uint64_t rows_capacity, int32_t *out, int32_t *pos,
+                            uint8_t *fresh, int32_t *lengths, int32_t *row_sentence, uint64_t *first_row,
+                            uint64_t *stats) {
+  spm_amd::WindowGeom g;
+  const int rc = WindowArgs(off, n, row_len, stride, flags, out, &rows_capacity, &g);
+  if (rc != SPM_OK) return rc;
+  spm_amd::DenseWindowHostLoop(ids, off, n, g, pad_id, rows_capacity, out, pos, fresh, lengths, row_sentence,
+                               first_row, stats);
   return SPM_OK;
 }
 

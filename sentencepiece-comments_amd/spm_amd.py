@@ -60,6 +60,7 @@ EXPORTED = [
     "spm_hip_model_byte_fallback", "spm_hip_finalize_ids_bytes", "spm_hip_finalize_ids_bytes_async",
     "spm_hip_pad_ids", "spm_hip_pack_ids", "spm_hip_pad_ids_host", "spm_hip_pack_ids_host",
     "spm_hip_fit_ids", "spm_hip_fit_ids_scratch_bytes", "spm_hip_fit_ids_host",
+    "spm_hip_window_ids", "spm_hip_window_ids_scratch_bytes", "spm_hip_window_ids_host",
     "spm_hip_split_lines", "spm_hip_split_lines_host", "spm_hip_format_id_rows", "spm_hip_format_id_rows_host",
     "spm_hip_format_piece_rows", "spm_hip_format_piece_rows_host",
 ]
@@ -70,6 +71,11 @@ DENSE_BLOCKS, DENSE_PACK_BLOCKS, DENSE_TILE_SLOTS = 1024, 2048, 1024
 # Fit (csrc/dense.h): sentences of a level-0 tile, tiles of a level per tile of the next, tiles one thread
 # walks at the top, chunks of the prefix scan.  SPM_HIP_FIT_GEOMETRY="branch,top_walk" is the test knob.
 FIT_TILE, FIT_BRANCH, FIT_TOP_WALK, FIT_SCAN_TILES = 4096, 16, 256, 1024
+# Flags of spm_hip_window_ids (include/spm_hip.h).
+SPM_WINDOW_KEEP_FIRST, SPM_WINDOW_KEEP_LAST = 1, 2
+# Window (csrc/dense_window.h): sentences of a scan tile, output slots of a fill chunk, sentences of a chunk
+# whose first rows fit into LDS.
+WINDOW_SCAN_TILE, WINDOW_CHUNK_SLOTS, WINDOW_SEG = 2048, 8192, 2048
 
 ABI_VERSION = 3  # SPM_HIP_ABI_VERSION of include/spm_hip.h (struct layouts below)
 
@@ -283,6 +289,9 @@ def lib():
         L.spm_hip_fit_ids.argtypes = [P, P, U64, U32, I32, U32, U64, P, P, P, P, P, P, P, U64, P]
         L.spm_hip_fit_ids_scratch_bytes.argtypes = [U64, U32, U64, P]
         L.spm_hip_fit_ids_host.argtypes = [P, P, U64, U32, I32, U32, U64, P, P, P, P, P, P]
+        L.spm_hip_window_ids.argtypes = [P, P, U64, U32, U32, I32, U32, U64, P, P, P, P, P, P, P, P, U64, P]
+        L.spm_hip_window_ids_scratch_bytes.argtypes = [U64, P]
+        L.spm_hip_window_ids_host.argtypes = [P, P, U64, U32, U32, I32, U32, U64, P, P, P, P, P, P, P]
         L.spm_hip_split_lines.argtypes = [P, U64, P, P, U64, P, P, P, P]
         L.spm_hip_split_lines_host.argtypes = [P, U64, P, P, U64, P]
         L.spm_hip_format_id_rows.argtypes = [P, P, U64, P, U64, P, P, P, P]
@@ -374,6 +383,34 @@ def fit_ids_device(d_ids, d_off, n, row_len, pad_id, flags, rows_capacity, d_out
     _check(lib().spm_hip_fit_ids(_vp(d_ids), _vp(d_off), n, row_len, pad_id, flags, rows_capacity, _vp(d_out),
                                  _vp(d_seq), _vp(d_pos), _vp(d_row_lengths), _vp(d_place), _vp(d_stats),
                                  _vp(d_scratch), scratch_bytes, _vp(stream)))
+
+
+def window_ids_scratch_bytes(n):
+    """spm_hip_window_ids_scratch_bytes: the device scratch one spm_hip_window_ids call needs (host only)."""
+    b = ctypes.c_uint64()
+    _check(lib().spm_hip_window_ids_scratch_bytes(n, ctypes.byref(b)))
+    return b.value
+
+
+def window_flags(keep_first=False, keep_last=False):
+    return (SPM_WINDOW_KEEP_FIRST if keep_first else 0) | (SPM_WINDOW_KEEP_LAST if keep_last else 0)
+
+
+def window_rows_bound(tokens, n, row_len, stride, keep_first=False, keep_last=False):
+    """Rows spm_hip_window_ids can need for n sentences of `tokens` ids in all: n + floor(tokens / step)."""
+    step = row_len - bool(keep_first) - bool(keep_last) - stride
+    if step < 1 or stride < 0:
+        raise SpmError(SPM_INVALID_ARGUMENT, "row_len leaves no payload beside the kept tokens, or stride >= the payload")
+    return n + tokens // step
+
+
+def window_ids_device(d_ids, d_off, n, row_len, stride, pad_id, flags, rows_capacity, d_out, d_scratch, scratch_bytes,
+                      d_pos=None, d_fresh=None, d_lengths=None, d_row_sentence=None, d_first_row=None, d_stats=None,
+                      stream=None):
+    """spm_hip_window_ids on device pointers (ints): a pure stream call, no model handle."""
+    _check(lib().spm_hip_window_ids(_vp(d_ids), _vp(d_off), n, row_len, stride, pad_id, flags, rows_capacity,
+                                    _vp(d_out), _vp(d_pos), _vp(d_fresh), _vp(d_lengths), _vp(d_row_sentence),
+                                    _vp(d_first_row), _vp(d_stats), _vp(d_scratch), scratch_bytes, _vp(stream)))
 
 
 TEXT_ROWS_SCRATCH_BYTES = 16384  # SPM_HIP_TEXT_ROWS_SCRATCH_BYTES
@@ -483,6 +520,27 @@ def fit_ids_host(ids, off, row_len, pad_id, flags=0, rows_capacity=None, fill=0)
     _check(lib().spm_hip_fit_ids_host(_p(ids), _p(off), n, row_len, pad_id, flags, rows_capacity, _p(out), _p(seq),
                                       _p(pos), _p(row_lengths), _p(place), _p(stats)))
     return out, seq, pos, row_lengths, place, stats
+
+
+def window_ids_host(ids, off, row_len, stride, pad_id, flags=0, rows_capacity=None, fill=0):
+    """spm_hip_window_ids_host on a numpy id CSR (no GPU): (out, pos int32[rows_capacity, L], fresh
+    uint8[rows_capacity, L], lengths, row_sentence int32[rows_capacity], first_row uint64[n+1], stats
+    uint64[2]).  rows_capacity None: window_rows_bound.  What the call leaves alone keeps `fill`."""
+    ids, off, n = _host_csr(ids, off)
+    L = int(row_len)
+    if rows_capacity is None:
+        rows_capacity = window_rows_bound(int(off[-1]) - int(off[0]), n, L, stride, flags & 1, flags & 2)
+    ok = 0 < L < (1 << 31)
+    shape, rows = ((max(int(rows_capacity), 1), L), int(rows_capacity)) if ok else ((1, 1), 0)
+    out, pos = (np.full(shape, fill, dtype=np.int32)[:rows] for _ in range(2))  # never a NULL base
+    fresh = np.full(shape, fill & 0xFF, dtype=np.uint8)[:rows]
+    lengths, row_sentence = (np.full(shape[0], fill, dtype=np.int32)[:rows] for _ in range(2))
+    first_row = np.zeros(n + 1, dtype=np.uint64)
+    stats = np.zeros(2, dtype=np.uint64)
+    _check(lib().spm_hip_window_ids_host(_p(ids), _p(off), n, row_len, stride, pad_id, flags, rows_capacity, _p(out),
+                                         _p(pos), _p(fresh), _p(lengths), _p(row_sentence), _p(first_row),
+                                         _p(stats)))
+    return out, pos, fresh, lengths, row_sentence, first_row, stats
 
 
 class DeviceModel:
@@ -1373,6 +1431,39 @@ class DeviceModel:
                        stats.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
         rows = int(stats[0].item())
         return ids[:rows], seq[:rows], pos[:rows], row_lengths[:rows]
+
+    def encode_lines_windowed(self, lines, row_len, pad_id, stride, keep_first=False, keep_last=False,
+                              extra_options="", sample=None):
+        """Raw lines -> (ids, pos int32[R, L], fresh bool[R, L], lengths,
+        row_sentence int32[R]) torch tensors on the current device: a line of
+        more than L ids becomes several rows that overlap by `stride` ids
+        (spm_hip_window_ids).  pos is the id's index in its line, fresh marks
+        the ids no earlier row carries (the ones to score or label),
+        row_sentence the row's line.  keep_first / keep_last repeat the line's
+        first / last id (a bos / eos of the extra options) in every row.  The
+        buffers are sized by window_rows_bound; the rows needed are read back
+        (the one synchronization) and the first R rows returned.  sample as in
+        encode_lines_padded."""
+        import torch
+        d_csr, d_ooff, k = self._lines_to_id_csr(lines, extra_options, sample)
+        dev, n, L = d_csr.device, len(lines), int(row_len)
+        if not 0 < L < (1 << 31):
+            raise SpmError(SPM_INVALID_ARGUMENT, "row_len must be in [1, INT32_MAX]")
+        cap = window_rows_bound(k, n, L, stride, keep_first, keep_last)
+        ids, pos = (torch.empty((cap, L), dtype=torch.int32, device=dev) for _ in range(2))
+        fresh = torch.empty((cap, L), dtype=torch.uint8, device=dev)
+        lengths, row_sentence = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(2))
+        if cap == 0:  # empty tensors have no base to pass
+            return ids, pos, fresh.view(torch.bool), lengths, row_sentence
+        nbytes = window_ids_scratch_bytes(n)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        stats = torch.empty(2, dtype=torch.int64, device=dev)
+        window_ids_device(d_csr.data_ptr(), d_ooff.data_ptr(), n, L, stride, pad_id,
+                          window_flags(keep_first, keep_last), cap, ids.data_ptr(), scratch.data_ptr(), nbytes,
+                          pos.data_ptr(), fresh.data_ptr(), lengths.data_ptr(), row_sentence.data_ptr(), None,
+                          stats.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        rows = int(stats[0].item())
+        return ids[:rows], pos[:rows], fresh[:rows].view(torch.bool), lengths[:rows], row_sentence[:rows]
 
 
 class DevicePieces:

@@ -13,8 +13,10 @@ Workloads: pad of c2 at L = 16, pad of botchan and wagahaiwa at L = 64 and
 L = 512 (all outputs: ids, lengths, mask, stats), pack of c2 and botchan at
 L = 2048 (ids, seq, pos, stats); fit (spm_hip_fit_ids, all outputs) of c2 at
 L = 16 and L = 2048 and of botchan and wagahaiwa at L = 512, timed in pairs
-with spm_hip_pack_ids on the same ids (--fit-only skips the rest).  Per
-workload, in one run:
+with spm_hip_pack_ids on the same ids (--fit-only skips the rest); window
+(spm_hip_window_ids, all outputs) of c2 at L = 16, S = 4, of botchan at
+L = 64, S = 16 and of wagahaiwa at L = 128, S = 32, likewise beside pack
+(--window-only skips the rest).  Per workload, in one run:
 
   * the kernel's time (HIP events around the stream call) and a restatement of
     the same result with torch ops on the same CSR on the device, warmed up and
@@ -49,6 +51,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--fit-only", action="store_true")
+    ap.add_argument("--window-only", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -208,6 +211,57 @@ def main():
                      "%.1f GB/s; device-to-device copy of that many bytes median %.3f ms"
                      % (name, k[0], k[1], k[2], moved, moved / (k[0] * 1e-3) / 1e9, statistics.median(c)))
 
+    def window(name, d_ids, d_off, L, S, pad_id=-1):
+        """spm_hip_window_ids (all outputs, no kept tokens) beside spm_hip_pack_ids at the same L on the same
+        ids, a device copy of the bytes it writes, and the one-thread host loop once."""
+        import time
+        n = d_off.numel() - 1
+        T = int((d_off[-1] - d_off[0]).item())
+        cap = spm_amd.window_rows_bound(T, n, L, S)
+        prow = (T + L - 1) // L
+        out, pos, seq = (torch.empty((max(cap, prow), L), dtype=torch.int32, device=dev) for _ in range(3))
+        fresh = torch.empty((cap, L), dtype=torch.uint8, device=dev)
+        lengths, rs = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(2))
+        first_row = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        stats = torch.empty(2, dtype=torch.int64, device=dev)
+        nbytes = spm_amd.window_ids_scratch_bytes(n)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+        def kernel():
+            spm_amd.window_ids_device(d_ids.data_ptr(), d_off.data_ptr(), n, L, S, pad_id, 0, cap, out.data_ptr(),
+                                      scratch.data_ptr(), nbytes, pos.data_ptr(), fresh.data_ptr(),
+                                      lengths.data_ptr(), rs.data_ptr(), first_row.data_ptr(), stats.data_ptr(),
+                                      stream=stream)
+
+        def packed():
+            spm_amd.pack_ids_device(d_ids.data_ptr(), d_off.data_ptr(), n, L, pad_id, prow, out.data_ptr(),
+                                    seq.data_ptr(), pos.data_ptr(), stream=stream)
+
+        times, _, _ = pairs(packed, kernel)
+        kernel()
+        torch.cuda.synchronize(dev)
+        R, multi = stats.tolist()
+        t0 = time.perf_counter()
+        h = spm_amd.window_ids_host(d_ids.cpu().numpy(), d_off.cpu().numpy().view(np.uint64), L, S, pad_id, 0,
+                                    rows_capacity=R)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        same = all(np.array_equal(a[:R].cpu().numpy(), b) for a, b in zip((out, pos, fresh, lengths, rs), h[:5]))
+        same = same and np.array_equal(first_row.cpu().numpy().view(np.uint64), h[5]) and [R, multi] == h[6].tolist()
+        written = 9 * R * L + 8 * R + 8 * (n + 1) + 16
+        src, dst = (torch.empty(written, dtype=torch.uint8, device=dev) for _ in range(2))
+        c = [timed(lambda: dst.copy_(src))[0] for _ in range(args.warmup + args.pairs)][args.warmup:]
+        cm, (p, k) = statistics.median(c), times
+        lines.append("%s: window, %d sentences, %d ids, L = %d, S = %d, %d rows (bound %d; pack: %d), %d sentences of "
+                     "several rows, %d bytes of scratch; equal to the host loop: %s"
+                     % (name, n, T, L, S, R, cap, prow, multi, nbytes, same))
+        lines.append("%s  kernels (stream call, HIP events) median %.3f ms (min %.3f, max %.3f): %d bytes written, "
+                     "%.1f GB/s; device-to-device copy of that many bytes median %.3f ms (min %.3f, max %.3f); "
+                     "window / copy = %.2f" % (name, k[0], k[1], k[2], written, written / (k[0] * 1e-3) / 1e9, cm,
+                                               min(c), max(c), k[0] / cm))
+        lines.append("%s  pack at the same L on the same ids median %.3f ms (min %.3f, max %.3f); window / pack = "
+                     "%.2f; one-thread host loop (with its buffers) %.1f ms"
+                     % (name, p[0], p[1], p[2], k[0] / p[0], host_ms))
+
     # c2: the synthetic batch, encoded on the device (model-level ids are final ids here: no extra options).
     buf, off = synth.normalized(args.sentences, seed=1234)
     dm = spm_amd.DeviceModel(open(os.path.join(ROOT, "data", "synth32k_unigram.model"), "rb").read())
@@ -220,11 +274,15 @@ def main():
     torch.cuda.synchronize(dev)
     c2_ids = c2_ids[:int(c2_off[-1].item())].clone()
     del d_bytes, d_boff, dm
-    if not args.fit_only:
+    only = args.fit_only or args.window_only
+    if not only:
         pad("c2 L=16", c2_ids, c2_off, 16)
         pack("c2 L=2048", c2_ids, c2_off, 2048)
-    fit("c2 L=16", c2_ids, c2_off, 16)
-    fit("c2 L=2048", c2_ids, c2_off, 2048)
+    if not args.window_only:
+        fit("c2 L=16", c2_ids, c2_off, 16)
+        fit("c2 L=2048", c2_ids, c2_off, 2048)
+    if not args.fit_only:
+        window("c2 L=16 S=4", c2_ids, c2_off, 16, 4)
     del c2_ids, c2_off
 
     gold = os.path.join(ROOT, "tests", "golden")
@@ -241,11 +299,15 @@ def main():
         d_ids = d_fin[:k].repeat(reps)
         d_off = torch.from_numpy(toff).to(dev)
         del dm, d_fin, d_foff
-        for L in () if args.fit_only else (64, 512):
+        for L in () if only else (64, 512):
             pad("%s x%d L=%d" % (name, reps, L), d_ids, d_off, L)
-        if name == "botchan" and not args.fit_only:
+        if name == "botchan" and not only:
             pack("%s x%d L=2048" % (name, reps), d_ids, d_off, 2048)
-        fit("%s x%d L=512" % (name, reps), d_ids, d_off, 512)
+        if not args.window_only:
+            fit("%s x%d L=512" % (name, reps), d_ids, d_off, 512)
+        if not args.fit_only:
+            L = 64 if name == "botchan" else 128
+            window("%s x%d L=%d S=%d" % (name, reps, L, L // 4), d_ids, d_off, L, L // 4)
         del d_ids, d_off
         torch.cuda.empty_cache()
 
