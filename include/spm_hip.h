@@ -271,12 +271,18 @@ int spm_hip_sample_uniform(uint64_t seed, uint64_t index, uint64_t draw, double 
  * SPM_UNIMPLEMENTED (unigram models sample with
  * spm_hip_sample_encode_batch, which in turn keeps answering
  * SPM_UNIMPLEMENTED for BPE models).  A host-only handle ->
- * SPM_FAILED_PRECONDITION.  n = 0 is fine.  spm_hip_model_last_stats reports
- * general_path = the sentences the literal kernel took: sentences of more
- * than 1024 bytes, those that probe an UNUSED piece or (models whose pieces
- * do not all split into pieces) hold a char outside the vocabulary, every
- * sentence of a model with USER_DEFINED pieces or under
- * spm_hip_model_set_force_general; both kernels give the same result. */
+ * SPM_FAILED_PRECONDITION.  n = 0 is fine.
+ *
+ * Tiers: the lane tier (models of < 32768 pieces: one sentence per lane, up
+ * to 34 chars and 255 bytes), the one-sentence-per-wave tier (<= 1024 bytes)
+ * over what the lane tier leaves, the literal kernel over what either
+ * refuses.  spm_hip_model_last_stats reports general_path = the sentences
+ * the literal kernel took: sentences of more than 1024 bytes, those that
+ * probe an UNUSED piece or (models whose pieces do not all split into
+ * pieces) hold a char outside the vocabulary, every sentence of a model with
+ * USER_DEFINED pieces or under spm_hip_model_set_force_general; every kernel
+ * gives the same result.  SPM_HIP_BPE_DROPOUT_LANE=0 in the environment (read
+ * once per process) leaves the lane tier out. */
 int spm_hip_bpe_dropout_encode_batch(spm_hip_model *model, const uint8_t *d_norm_bytes,
                                      const uint64_t *d_offsets, uint64_t n, float alpha, uint64_t seed,
                                      uint64_t index_base, int32_t *d_ids, uint32_t *d_piece_len,
@@ -289,6 +295,13 @@ int spm_hip_bpe_dropout_encode_batch_host(spm_hip_model *model, const uint8_t *n
 /* Host only: the integer threshold of alpha, ceil((double) alpha * 2^53)
  * clamped to [0, 2^53].  NaN -> SPM_INVALID_ARGUMENT. */
 int spm_hip_bpe_dropout_threshold(float alpha, uint64_t *threshold);
+/* Of the last blocking BPE-dropout call on the handle: the sentences each
+ * tier finished (lane_tier + wave_tier + literal = the batch, literal =
+ * general_path).  Counted on the device and published together with
+ * spm_hip_model_last_stats; all three are 0 after a blocking call that is
+ * not BPE-dropout.  Any pointer may be NULL. */
+int spm_hip_bpe_dropout_last_stats(const spm_hip_model *model, uint64_t *lane_tier, uint64_t *wave_tier,
+                                   uint64_t *literal);
 
 /* Batched SentencePieceProcessor::CalculateEntropy of the `sentencepiece`
  * package (0.2.x): the entropy of every sentence's segmentation distribution

@@ -19,7 +19,9 @@
 //   wave, 64 KiB per block: two blocks per CU.  The short instantiation
 //   (kBpeDropShortBytes: 2 KiB per wave) takes the sentences up to its bound
 //   and lists the others in `rest` for the full one.  Sentences the wave does
-//   not take are flagged for bpe_general_kernel<true>.
+//   not take are flagged for bpe_general_kernel<true>.  Behind
+//   bpe_lane_dropout_kernel (bpe_kernels.hip: one sentence per lane, models of
+//   < 32768 pieces) both passes take that kernel's rest list, not the batch.
 #include <hip/hip_runtime.h>
 
 #include "bpe_device.h"
@@ -31,10 +33,12 @@ namespace {
 
 constexpr int kDropWaves = 4;
 
-// kShort: every sentence of the batch, the longer ones to `rest`; else the
-// sentences of `rest` (every sentence when rest == nullptr).
+// The sentences of `list` (every sentence of the batch when list == nullptr);
+// kShort: the ones over kMaxBytes bytes go to d.rest, else they are flagged.
 template <uint32_t kMaxBytes, bool kShort>
-__global__ __launch_bounds__(64 * kDropWaves) void bpe_dropout_kernel(BpeDropoutLaunch d) {
+__global__ __launch_bounds__(64 * kDropWaves) void bpe_dropout_kernel(BpeDropoutLaunch d,
+                                                                      const uint32_t *__restrict__ list,
+                                                                      const uint32_t *__restrict__ list_count) {
   __shared__ BpeLineSymsT<kMaxBytes> slab[kDropWaves];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if ((d.chain && *d.chain) || d.off[d.n] > d.capacity) {  // (BpeSkip of bpe_kernels.hip)
@@ -62,10 +66,10 @@ __global__ __launch_bounds__(64 * kDropWaves) void bpe_dropout_kernel(BpeDropout
   a.status = d.status;
   const uint64_t wave = static_cast<uint64_t>(blockIdx.x) * kDropWaves + wv;
   const uint64_t nwaves = static_cast<uint64_t>(gridDim.x) * kDropWaves;
-  const bool listed = !kShort && d.rest != nullptr;
-  const uint64_t count = listed ? *d.rest_count : d.n;
+  const uint64_t count = list ? *list_count : d.n;
+  uint32_t done = 0;
   for (uint64_t jl = wave; jl < count; jl += nwaves) {
-    const uint64_t i = listed ? d.rest[jl] : jl;
+    const uint64_t i = list ? list[jl] : jl;
     const uint64_t b0 = d.off[i];
     const uint64_t nb64 = d.off[i + 1] - b0;
     if (nb64 > kMaxBytes) {
@@ -83,7 +87,9 @@ __global__ __launch_bounds__(64 * kDropWaves) void bpe_dropout_kernel(BpeDropout
       if (nt == kNone) FlagSentence(a, i, nb);
       else a.ntok[i] = nt;
     }
+    done += nt != kNone ? 1u : 0u;
   }
+  if (lane == 0 && done) atomicAdd(&d.status[kStBpeDropWave], done);
 }
 
 }  // namespace
@@ -94,12 +100,17 @@ hipError_t LaunchBpeDropout(const BpeDropoutLaunch &d, hipStream_t st) {
   // either slab size.
   const uint64_t blocks64 = (d.n + kDropWaves - 1) / kDropWaves;
   const unsigned blocks = static_cast<unsigned>(blocks64 < 8192 ? blocks64 : 8192);
+  const uint32_t *list = d.list, *list_count = d.list_count;
   if (d.rest) {
-    hipLaunchKernelGGL((bpe_dropout_kernel<kBpeDropShortBytes, true>), dim3(blocks), dim3(64 * kDropWaves), 0, st, d);
+    hipLaunchKernelGGL((bpe_dropout_kernel<kBpeDropShortBytes, true>), dim3(blocks), dim3(64 * kDropWaves), 0, st, d,
+                       list, list_count);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    list = d.rest;
+    list_count = d.rest_count;
   }
-  hipLaunchKernelGGL((bpe_dropout_kernel<kBpeLineMaxBytes, false>), dim3(blocks), dim3(64 * kDropWaves), 0, st, d);
+  hipLaunchKernelGGL((bpe_dropout_kernel<kBpeLineMaxBytes, false>), dim3(blocks), dim3(64 * kDropWaves), 0, st, d,
+                     list, list_count);
   return hipGetLastError();
 }
 

@@ -14,6 +14,10 @@
 //   pairs.  A wave then does 64 sentences' merges with the VALU work of one
 //   sequential merge each, where the wave-per-sentence kernels below spend a
 //   wave-wide reduction and scalar chain per merge of one or two sentences.
+// bpe_lane_dropout_kernel — the same tiles for BPE-dropout (SampleEncode):
+//   every probed pair masked by the sentence's draw stream, the pair's byte
+//   offsets re-derived from the chars' 2-bit lengths; the first tier of a
+//   dropout call, ahead of bpe_dropout_kernel (bpe_dropout.hip).
 // bpe_fast_kernel — one sentence per wavefront, one byte (= one initial
 //   symbol for ASCII, one char start otherwise) per lane, symbol state in
 //   VGPRs, the live set as a wave-uniform 64-bit mask.  Per merge: a DPP
@@ -297,9 +301,30 @@ __device__ __forceinline__ uint32_t SymWord(int32_t sym, int32_t pres) {
 // 16-bit symbol and the winner's merged id comes from the rank -> piece
 // table (one L1-resident load per merge): 17.5 KB of LDS per tile instead of
 // 25.5 KB, 9 tiles per CU instead of 6 (4 waves per SIMD instead of 3).
-template <bool kRankIds>
-__global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__restrict__ rest,
-                                                       uint32_t *__restrict__ rest_count) {
+//
+// kDrop — bpe_lane_dropout_kernel, BPE-dropout (SampleEncode) on the same
+// columns: the arg-max runs over the live adjacent pairs that have not been
+// dropped.  A pair is masked when it is probed, as in BpeEncodeLineWave: the
+// initial pairs (k, k + 1) and the two new pairs (P, L) and (L, RR) of every
+// merge; a dropped pair gets key 0 (and, in the 32-bit layout, no merged id),
+// after its UNUSED bit has flagged the sentence.  The pair of column c is
+// named by the byte offset of char c and the byte offset of the second live
+// column after c (nb when there is none), and the columns keep no offsets:
+// char k starts at byte k + sum over j < k of (len_j - 1), two popcounts over
+// the 2-bit clen / clen_hi fields below k.  That costs ~12 VALU instructions
+// per offset and no LDS; a uint8 start column would add 4.25 KB per tile
+// (rank ids: 6 tiles per CU instead of 8, 32-bit words: 4 instead of 5).
+// The draws' key is a lane's own (SampleKey(seed, index_base + i)), so a row
+// depends on (seed, global index, sentence, alpha) only.  d.done counts the
+// sentences the tier finished.
+struct BpeLaneDrop {
+  uint64_t threshold, seed, index_base;
+  uint32_t *done;
+};
+
+template <bool kRankIds, bool kDrop>
+__device__ __forceinline__ void BpeLaneTiles(BpeArgs a, uint32_t *__restrict__ rest,
+                                             uint32_t *__restrict__ rest_count, BpeLaneDrop d) {
   // 25.5 KB of LDS per 128-lane tile (6 tiles, 3 waves per SIMD): pair keys
   // are 16-bit score ranks, and the chars' byte offsets are re-derived from
   // the sentence at output instead of being stored.
@@ -432,6 +457,22 @@ __global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__re
         q += L;
       }
     }
+    // kDrop: the sentence's draw stream, and whether the pair of column c
+    // and the next live column of lv (there is one) is dropped.
+    BpeDropKey drop{};
+    if constexpr (kDrop) drop = BpeDropKey{SampleKey(d.seed, d.index_base + i), d.threshold};
+    auto start_of = [&](uint32_t k) -> uint32_t {  // byte offset of char k; of k == nch: nb
+      const uint64_t lo = k >= 32 ? clen : clen & ((1ull << (2 * k)) - 1ull);
+      const uint32_t hi = k > 32 ? clen_hi & ((1u << (2 * (k - 32))) - 1u) : 0u;
+      return k + static_cast<uint32_t>(__popcll(lo & 0x5555555555555555ull) + 2 * __popcll(lo & 0xAAAAAAAAAAAAAAAAull) +
+                                       __popc(hi & 0x55555555u) + 2 * __popc(hi & 0xAAAAAAAAu));
+    };
+    auto pair_dropped = [&](uint64_t lv, int c) -> bool {
+      const uint64_t right = lv & ~((2ull << c) - 1ull);  // its lowest bit: the pair's right symbol
+      const uint64_t past = right & (right - 1ull);
+      return BpeDropped(drop, start_of(static_cast<uint32_t>(c)),
+                        start_of(past ? static_cast<uint32_t>(__builtin_ctzll(past)) : nch));
+    };
     if (elig) {
       // Pairs (k, k + 1) of in-vocabulary symbols, kPairBatch probes issued
       // together; a probe that meets another key walks on alone.
@@ -471,6 +512,15 @@ __global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__re
           if ((x.z >> 31) != 0) bad = true;
         });
       }
+      // kDrop: the mask of the initial pairs, after their UNUSED bits have
+      // been seen (rev_merge records dropped pairs too).
+      if constexpr (kDrop) {
+        for (uint32_t k = 0; k + 1 < nch; ++k) {
+          if (lkey[k * kLB + tid] == 0u || !pair_dropped((1ull << nch) - 1ull, static_cast<int>(k))) continue;
+          lkey[k * kLB + tid] = 0u;
+          if constexpr (!kRankIds) lsp[k * kLB + tid] = SymWord(SymOf(static_cast<uint32_t>(lsp[k * kLB + tid])), -1);
+        }
+      }
     }
     // Columns past the lane's chars hold an earlier tile's keys: zero them
     // once, so the merge scan reads whole groups of columns unconditionally.
@@ -503,7 +553,7 @@ __global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__re
           for (int q = 0; q < kLaneChars; ++q) bm = max(bm, (v[q] << 6) | static_cast<uint32_t>(63 - q));
         }
         if (pend) {
-          auto resolve = [&](int32_t l, int32_t r, uint32_t h, uint4 e, uint32_t *key, bool *unused) {
+          auto resolve = [&](int32_t l, int32_t r, uint32_t h, uint4 e, int col, uint32_t *key, bool *unused) {
             *key = 0u;
             *unused = false;
             if (l < 0 || r < 0) return;
@@ -514,11 +564,14 @@ __global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__re
             }
             *key = e.w;
             *unused = (e.z >> 31) != 0;
+            if constexpr (kDrop) {  // (live is as the merge left it: col's pair is the probed one)
+              if (pair_dropped(live, col)) *key = 0u;
+            }
           };
           uint32_t kP, kL;
           bool uP, uL;
-          resolve(l0, r0, h0, e0, &kP, &uP);
-          resolve(l1, r1, h1, e1, &kL, &uL);
+          resolve(l0, r0, h0, e0, qP, &kP, &uP);
+          resolve(l1, r1, h1, e1, qL, &kL, &uL);
           if (qP >= 0) {
             lkey[qP * kLB + tid] = static_cast<uint16_t>(kP);
             bm = max(bm, (kP << 6) | static_cast<uint32_t>(63 - qP));
@@ -603,13 +656,19 @@ __global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__re
           uint32_t kP, kL;
           bool uP, uL;
           PairLookupFused2(a, SymOf(wP), merged, Pk >= 0, merged, symRR, RRk >= 0, &mP, &kP, &uP, &mL, &kL, &uL);
+          bool unused_push = false;
+          if constexpr (kDrop) {  // (the UNUSED bits before the mask: rev_merge records dropped pairs too)
+            unused_push = (mP >= 0 && uP) || (mL >= 0 && uL);
+            if (mP >= 0 && pair_dropped(live, Pk)) mP = -1;
+            if (mL >= 0 && pair_dropped(live, Lk)) mL = -1;
+          }
           if (Pk >= 0) {
             lkey[Pk * kLB + tid] = static_cast<uint16_t>(mP >= 0 ? kP : 0u);
             if constexpr (!kRankIds) lsp[Pk * kLB + tid] = SymWord(SymOf(wP), mP);
           }
           lkey[Lk * kLB + tid] = static_cast<uint16_t>(mL >= 0 ? kL : 0u);
           lsp[Lk * kLB + tid] = kRankIds ? static_cast<SymT>(merged & 0xFFFF) : static_cast<SymT>(SymWord(merged, mL));
-          if ((mP >= 0 && uP) || (mL >= 0 && uL)) {
+          if (unused_push || (mP >= 0 && uP) || (mL >= 0 && uL)) {
             bad = true;
             act = false;
           }
@@ -623,6 +682,10 @@ __global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__re
     // The pair-key columns (dead after the merges) hold the ids, the sort
     // table the piece lengths; tokens past the staging room go straight out.
     const bool mine = valid && elig && !bad;
+    if constexpr (kDrop) {
+      const uint32_t done = static_cast<uint32_t>(__popcll(__ballot(mine)));
+      if (lane == 0 && done) atomicAdd(d.done, done);
+    }
     const uint32_t nt = mine && nch ? static_cast<uint32_t>(__popcll(live)) : 0u;
     uint32_t *const lcnt = lds_sort;  // [sid]: token count, then tile-local offset
     uint32_t *const stage_id = reinterpret_cast<uint32_t *>(lkey);
@@ -695,6 +758,18 @@ __global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__re
     }
     __syncthreads();  // the next tile reuses the LDS columns
   }
+}
+
+template <bool kRankIds>
+__global__ __launch_bounds__(kLB) void bpe_lane_kernel(BpeArgs a, uint32_t *__restrict__ rest,
+                                                       uint32_t *__restrict__ rest_count) {
+  BpeLaneTiles<kRankIds, false>(a, rest, rest_count, BpeLaneDrop{});
+}
+
+template <bool kRankIds>
+__global__ __launch_bounds__(kLB) void bpe_lane_dropout_kernel(BpeArgs a, uint32_t *__restrict__ rest,
+                                                               uint32_t *__restrict__ rest_count, BpeLaneDrop d) {
+  BpeLaneTiles<kRankIds, true>(a, rest, rest_count, d);
 }
 
 // One sentence per wavefront, over the sentences the half kernel left in
@@ -1361,8 +1436,9 @@ hipError_t LaunchBpeCompact(const uint64_t *off, uint64_t n, const uint32_t *nto
 // Models with user-defined symbols (BpeDevice::frozen_ok): bpe_frozen_kernel
 // (bpe_frozen.hip) over every sentence in place of all of the above, then the
 // literal kernels over the list it hands on.
-// c.drop (BPE-dropout): bpe_dropout_kernel (bpe_dropout.hip) in place of the
-// lane / half / fast kernels and bpe_general_kernel<true> for what it flags.
+// c.drop (BPE-dropout): bpe_lane_dropout_kernel (models of < 32768 pieces),
+// then bpe_dropout_kernel (bpe_dropout.hip) over its rest list, in place of
+// the lane / half / fast kernels, and bpe_general_kernel<true> for what they flag.
 int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::string *err) {
 #define BPE_TRY(expr)                                              \
   do {                                                             \
@@ -1407,6 +1483,10 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
   // word tier.
   static const int kTextKnob = [] {
     const char *e = std::getenv("SPM_HIP_BPE_TEXT");
+    return e ? std::atoi(e) : 1;
+  }();
+  static const int kRankIdsKnob = [] {  // A/B knob: SPM_HIP_BPE_RANK_IDS=0 keeps the 32-bit symbol words
+    const char *e = std::getenv("SPM_HIP_BPE_RANK_IDS");
     return e ? std::atoi(e) : 1;
   }();
   const BpeDropout drop = c.drop ? *c.drop : BpeDropout{};
@@ -1487,6 +1567,33 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
       d.index_base = drop.index_base;
       d.rest = kShortKnob ? ws->w_rest.as<uint32_t>() : nullptr;
       d.rest_count = kShortKnob ? status + kStBpeRest : nullptr;
+      // The lane tier first (one sentence per lane: ids fit the columns'
+      // 16 bits) unless SPM_HIP_BPE_DROPOUT_LANE=0 (A/B knob); the wave
+      // passes then take its rest list, the short one listing into a second.
+      static const int kLaneKnob = [] {
+        const char *e = std::getenv("SPM_HIP_BPE_DROPOUT_LANE");
+        return e ? std::atoi(e) : 1;
+      }();
+      if (m->bpe.lane_ok && kLaneKnob) {
+        BPE_TRY(ws->w_slot_ids.Reserve(cap * 4));
+        if (c.len) BPE_TRY(ws->w_slot_len.Reserve(cap * 4));
+        BPE_TRY(ws->w_bpe_wave.Reserve(nn * 4));
+        a.lane_ids = ws->w_slot_ids.as<int32_t>();
+        a.lane_len = c.len ? ws->w_slot_len.as<uint32_t>() : nullptr;
+        const BpeLaneDrop ld{drop.threshold, drop.seed, drop.index_base, status + kStBpeDropLane};
+        const dim3 grid(static_cast<unsigned>(std::min<uint64_t>((n + kLB - 1) / kLB, 1u << 20)));
+        if (m->bpe.rank_ids && kRankIdsKnob)
+          hipLaunchKernelGGL(bpe_lane_dropout_kernel<true>, grid, dim3(kLB), 0, st, a, ws->w_rest.as<uint32_t>(),
+                             status + kStBpeRest, ld);
+        else
+          hipLaunchKernelGGL(bpe_lane_dropout_kernel<false>, grid, dim3(kLB), 0, st, a, ws->w_rest.as<uint32_t>(),
+                             status + kStBpeRest, ld);
+        BPE_TRY(hipGetLastError());
+        d.list = ws->w_rest.as<uint32_t>();
+        d.list_count = status + kStBpeRest;
+        d.rest = kShortKnob ? ws->w_bpe_wave.as<uint32_t>() : nullptr;
+        d.rest_count = kShortKnob ? status + kStBpeDropRest : nullptr;
+      }
       BPE_TRY(LaunchBpeDropout(d, st));
     } else if (kFastOnly) {
       // (nothing first: bpe_fast_kernel below takes every sentence)
@@ -1496,10 +1603,6 @@ int EncodeBpe(spm_hip_model *m, EncodeWorkspace *ws, const EncodeCall &c, std::s
       a.lane_ids = ws->w_slot_ids.as<int32_t>();
       a.lane_len = c.len ? ws->w_slot_len.as<uint32_t>() : nullptr;
       const uint64_t tiles = (n + kLB - 1) / kLB;
-      static const int kRankIdsKnob = [] {  // A/B knob: SPM_HIP_BPE_RANK_IDS=0 keeps the 32-bit symbol words
-        const char *e = std::getenv("SPM_HIP_BPE_RANK_IDS");
-        return e ? std::atoi(e) : 1;
-      }();
       const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(tiles, 1u << 20)));
       if (m->bpe.rank_ids && kRankIdsKnob)
         hipLaunchKernelGGL(bpe_lane_kernel<true>, grid, dim3(kLB), 0, st, a, ws->w_rest.as<uint32_t>(), status + kStBpeRest);

@@ -231,6 +231,9 @@ struct spm_hip_model {
   // finished them (pool_mu); their sum is last_stats.general_path.
   uint64_t bpe_word_tier = 0, bpe_wave_tier = 0, bpe_literal = 0;
   uint64_t bpe_frozen_taken = 0, bpe_frozen_handed = 0;  // the frozen-symbol tier's share of that Encode
+  // The last blocking BPE-dropout call: the sentences the lane tier, the wave
+  // passes and the literal kernel finished (0 after any other call).
+  uint64_t bpe_drop_lane = 0, bpe_drop_wave = 0, bpe_drop_literal = 0;
   std::atomic<uint32_t> nbest_hyps1{0}, nbest_hyps2{0};  // spm_hip_model_set_nbest_max_hyps
   int device = 0;
 };

@@ -36,6 +36,10 @@ enum : int {
   // BPE frozen-symbol tier (bpe_frozen.hip; the text tiers do not run then):
   kStBpeFrozenDone = 10, // sentences the frozen tier finished
   kStBpeFrozenRest = 11, // sentences its short-state launch left to the full one
+  // BPE-dropout (bpe_dropout.hip; the text tiers do not run then):
+  kStBpeDropRest = 11,   // behind the lane tier: sentences the short-slab wave pass left to the full one
+  kStBpeDropLane = 13,   // sentences the lane tier finished
+  kStBpeDropWave = 14,   // sentences the wave passes finished
   kStWords = 16
 };
 
@@ -535,6 +539,9 @@ hipError_t LaunchBpeRaw(const BpeRawArgs &s, const CoopCall &c, hipStream_t st);
 // rest / rest_count (nullable, zeroed count): with them the sentences of <=
 // kBpeDropShortBytes bytes run first on slabs of that size (more waves per
 // CU) and the longer ones from the `rest` list on full slabs.
+// list / list_count (nullable): the sentences the tier takes, the list that
+// bpe_lane_dropout_kernel (bpe_kernels.hip) left; null: every sentence.
+// status[kStBpeDropWave] counts the sentences the tier finished.
 constexpr uint32_t kBpeDropShortBytes = 128;
 struct BpeDropoutLaunch {
   BpeLineArgs t;
@@ -547,6 +554,7 @@ struct BpeDropoutLaunch {
   const uint32_t *chain;     // asynchronous chain status (nullable)
   uint64_t threshold, seed, index_base;
   uint32_t *rest, *rest_count;
+  const uint32_t *list, *list_count;
 };
 hipError_t LaunchBpeDropout(const BpeDropoutLaunch &d, hipStream_t st);
 

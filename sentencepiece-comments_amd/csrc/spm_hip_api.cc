@@ -517,8 +517,10 @@ int LongestSentence(const uint64_t *d_off, uint64_t n, hipStream_t st, uint32_t 
 // bpe_done (BPE Encode, else nullptr): the flagged sentences the word, the
 // wave and the frozen-symbol tier finished; published with the stats under one lock, so that
 // their sum with the literal kernel's share is this call's general_path.
+// drop_done (BPE-dropout, else nullptr): the sentences the lane tier and the
+// wave passes finished, published the same way.
 int PublishTierStats(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n, bool host_sized, uint32_t flagged,
-                     const uint64_t *bpe_done = nullptr) {
+                     const uint64_t *bpe_done = nullptr, const uint64_t *drop_done = nullptr) {
   ws->stats.sentences = n;
   ws->stats.general_path = host_sized ? n : flagged;
   if (m->timing && ws->last_slot >= 0) {
@@ -528,11 +530,16 @@ int PublishTierStats(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n,
     ws->tcount = 0;  // consumed here; the ring is for the asynchronous entry point
   }
   if (!bpe_done) {
-    spm_amd::PublishStats(m, ws->stats);
+    std::lock_guard<std::mutex> lk(m->pool_mu);
+    m->last_stats = ws->stats;
+    m->bpe_drop_lane = drop_done && !host_sized ? drop_done[0] : 0;
+    m->bpe_drop_wave = drop_done && !host_sized ? drop_done[1] : 0;
+    m->bpe_drop_literal = drop_done ? ws->stats.general_path : 0;
     return SPM_OK;
   }
   std::lock_guard<std::mutex> lk(m->pool_mu);
   m->last_stats = ws->stats;
+  m->bpe_drop_lane = m->bpe_drop_wave = m->bpe_drop_literal = 0;
   m->bpe_word_tier = host_sized ? 0 : bpe_done[0];
   m->bpe_wave_tier = host_sized ? 0 : bpe_done[1];
   m->bpe_literal = ws->stats.general_path - m->bpe_word_tier - m->bpe_wave_tier;
@@ -1039,6 +1046,8 @@ int EncodeBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t
   const bool frozen = bpe_tiers && m->bpe.frozen_ok && !c.host_sized;
   const uint64_t bpe_done[3] = {ws->pinned[spm_amd::kStBpeWordDone], ws->pinned[spm_amd::kStBpeWaveDone],
                                 frozen ? ws->pinned[spm_amd::kStBpeFrozenDone] : 0};
+  // BPE-dropout: the sentences the lane tier and the wave passes finished.
+  const uint64_t drop_done[2] = {ws->pinned[spm_amd::kStBpeDropLane], ws->pinned[spm_amd::kStBpeDropWave]};
   if (err && !c.host_sized) {
     c.host_sized = true;
     rc = LongestSentence(d_off, n, st, &c.max_nb);
@@ -1051,7 +1060,8 @@ int EncodeBlocking(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, const uint8_t
   }
   if (err) return Fail(SPM_INTERNAL, "general encode path: scratch overflow");
   ws->stats.coop_rest = c.host_sized ? 0 : ws->pinned[spm_amd::kStCoopRest];
-  return PublishTierStats(m, ws, n, c.host_sized, flagged, bpe_tiers ? bpe_done : nullptr);
+  return PublishTierStats(m, ws, n, c.host_sized, flagged, bpe_tiers ? bpe_done : nullptr,
+                          drop ? drop_done : nullptr);
 }
 
 // Lazy device tables of the normalizer (charsmap blob, user-defined trie).
@@ -1378,6 +1388,7 @@ WorkspaceLease::~WorkspaceLease() {
 void PublishStats(spm_hip_model *m, const spm_hip_encode_stats &s) {
   std::lock_guard<std::mutex> g(m->pool_mu);
   m->last_stats = s;
+  m->bpe_drop_lane = m->bpe_drop_wave = m->bpe_drop_literal = 0;
 }
 
 }  // namespace spm_amd
@@ -2768,7 +2779,8 @@ int FetchHostBatch(spm_hip_model *m, spm_amd::EncodeWorkspace *ws, uint64_t n, i
     SPM_HIP_TRY(hipStreamSynchronize(st));
   }
   ws->stats.tokens = ntok;
-  spm_amd::PublishStats(m, ws->stats);
+  std::lock_guard<std::mutex> lk(m->pool_mu);  // (the call's tier counts were published with its stats: they stay)
+  m->last_stats = ws->stats;
   return SPM_OK;
 }
 
@@ -3543,6 +3555,16 @@ int spm_hip_bpe_tier_last_stats(const spm_hip_model *m, uint64_t *word_tier, uin
   if (word_tier) *word_tier = m->bpe_word_tier;
   if (wave_tier) *wave_tier = m->bpe_wave_tier;
   if (literal) *literal = m->bpe_literal;
+  return SPM_OK;
+}
+
+int spm_hip_bpe_dropout_last_stats(const spm_hip_model *m, uint64_t *lane_tier, uint64_t *wave_tier,
+                                   uint64_t *literal) {
+  if (!m) return Fail(SPM_INVALID_ARGUMENT, "null argument");
+  std::lock_guard<std::mutex> lk(const_cast<spm_hip_model *>(m)->pool_mu);
+  if (lane_tier) *lane_tier = m->bpe_drop_lane;
+  if (wave_tier) *wave_tier = m->bpe_drop_wave;
+  if (literal) *literal = m->bpe_drop_literal;
   return SPM_OK;
 }
 

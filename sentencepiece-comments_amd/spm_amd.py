@@ -50,6 +50,7 @@ EXPORTED = [
     "spm_hip_encode_raw_small_host", "spm_hip_model_piece_lookup",
     "spm_hip_sample_encode_batch", "spm_hip_sample_encode_batch_host", "spm_hip_sample_uniform",
     "spm_hip_bpe_dropout_encode_batch", "spm_hip_bpe_dropout_encode_batch_host", "spm_hip_bpe_dropout_threshold",
+    "spm_hip_bpe_dropout_last_stats",
     "spm_hip_entropy_batch", "spm_hip_entropy_batch_host", "spm_hip_sample_encode_and_score_batch",
     "spm_hip_sample_encode_and_score_batch_host", "spm_hip_sample_seed",
     "spm_hip_nbest_encode_batch", "spm_hip_nbest_encode_batch_host", "spm_hip_model_set_nbest_max_hyps",
@@ -255,6 +256,7 @@ def lib():
         L.spm_hip_model_bpe_word_closed.argtypes = [P, ctypes.POINTER(ctypes.c_int)]
         L.spm_hip_bpe_tier_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_bpe_frozen_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]
+        L.spm_hip_bpe_dropout_last_stats.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64), ctypes.POINTER(U64)]
         L.spm_hip_device_peak_reset.restype = None
         L.spm_hip_decode_batch.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, ctypes.POINTER(U64), P]
         L.spm_hip_decode_batch_async.argtypes = [P, ctypes.c_char_p, P, P, U64, P, U64, P, P, P, P]
@@ -1095,6 +1097,13 @@ class DeviceModel:
         blocking BPE Encode by the tier that finished them."""
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         _check(self._L.spm_hip_bpe_tier_last_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def bpe_dropout_stats(self):
+        """(lane_tier, wave_tier, literal): the sentences of the last blocking
+        BPE-dropout call by the tier that finished them."""
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._L.spm_hip_bpe_dropout_last_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
 
     def bpe_frozen_stats(self):

@@ -11,7 +11,8 @@ Workloads: c3 (bench.py's BPE leg: synthetic sentences of tools/synth.py seed
 tests/golden/botchan.txt under botchan_bpe1k.model, repeated to --sentences).
 
 The kernels' A/B knobs are read once per process, so one process measures one
-configuration: SPM_HIP_BPE_DROPOUT_SHORT=0 turns the short-slab pass off,
+configuration: SPM_HIP_BPE_DROPOUT_LANE=0 leaves the lane tier out,
+SPM_HIP_BPE_DROPOUT_SHORT=0 turns the short-slab pass off,
 SPM_HIP_BPE_FAST_ONLY=1 runs bpe_fast_kernel alone for the plain encode (one
 sentence per wave, the like-for-like yardstick).  --package DIR imports
 spm_amd from another build (a parent commit's); --no-dropout measures the
@@ -80,8 +81,8 @@ def main():
     runs = [("encode", plain)]
     if not args.no_dropout:
         runs += [("dropout alpha %s" % a, dropout(float(a))) for a in args.alphas.split(",")]
-    knobs = " ".join("%s=%s" % (k, os.environ[k]) for k in ("SPM_HIP_BPE_DROPOUT_SHORT", "SPM_HIP_BPE_FAST_ONLY")
-                     if k in os.environ)
+    knobs = " ".join("%s=%s" % (k, os.environ[k]) for k in ("SPM_HIP_BPE_DROPOUT_LANE", "SPM_HIP_BPE_DROPOUT_SHORT",
+                                                            "SPM_HIP_BPE_FAST_ONLY") if k in os.environ)
     out = ["%s%s: %d sentences, %d bytes (mean %.1f, max %d, over 128 bytes: %.2f %%), model %s, %d launches after "
            "%d warm-up%s" % (args.label + ": " if args.label else "", args.workload, n, total, lens.mean(), lens.max(),
                              100.0 * float((lens > 128).mean()), os.path.basename(model), args.launches, args.warmup,
@@ -90,18 +91,20 @@ def main():
     for name, fn in runs:
         for k in range(args.warmup):
             fn(k)
-        ms, general, tokens = [], 0, 0
+        ms, general, tokens, tiers = [], 0, 0, ""
         for k in range(args.launches):
             fn(args.warmup + k)
             st = dm.stats()
             ms.append(float(st.fast_kernel_ms))
             general = int(st.general_path)
             tokens = int(d_tok[-1].item())
+            if name != "encode" and hasattr(dm, "bpe_dropout_stats"):  # (a parent build has no tier counts)
+                tiers = "  lane / wave / literal %d / %d / %d" % dm.bpe_dropout_stats()
         med = statistics.median(ms)
         base = base or med
         out.append("  %-18s median %9.3f ms (min %9.3f, max %9.3f)  %.3e sentences/s  x%.2f of encode  tokens %d  "
-                   "general tier %d of %d (%.4f %%)" % (name, med, min(ms), max(ms), n / (med * 1e-3), med / base,
-                                                        tokens, general, n, 100.0 * general / n))
+                   "general tier %d of %d (%.4f %%)%s" % (name, med, min(ms), max(ms), n / (med * 1e-3), med / base,
+                                                          tokens, general, n, 100.0 * general / n, tiers))
     text = "\n".join(out) + "\n"
     sys.stdout.write(text)
     if args.out:
